@@ -2,6 +2,7 @@
 """bench.py -- LR-Ref image pairs / second of the MI355X restoration path on synthetic 160x160-LR / 500x500-Ref pairs.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload restore|corr|train] [--lr 160] [--dtype f32|bf16]
+                    [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[2], the configuration the metric is quoted on: "Batch-16 full restoration forward
 (correlation + DCNv2 warp + decoder), 1xMI355X, fp32".  One "step" = one pass over one batch of B=16 pairs per GPU:
@@ -21,11 +22,19 @@ torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  Every rank works
 data-path collective: pairs are independent -- SURVEY.md 8e); barrier / max-over-ranks timing use RCCL.
 
 Prints ONE JSON line (rank 0): the contract fields, `stage_ms`, `roofline` (the hand-written kernel family with the largest
-share of the step) + `roofline_kernels` (every hand-written hot kernel: HIP events on the launch stream through
-c2m_profile_*; `frac` = EXECUTED matrix flops / peak of the pipe they run on, always <= 1; algorithmic-equivalent rates in
-their own keys), `configs1_corr_only` (the round-1 headline, kept as a sub-record) and `cpu_baseline` (the same forward on
-the host cores through oracle/cpu_chain.py, outside the timed region, with the GPU-vs-CPU parity of three pairs of the
-timed batch).
+share of the step) + `kernel_table` (every hand-written hot kernel: HIP events on the launch stream through
+c2m_profile_*, recorded during the timed steps themselves; `frac` = EXECUTED matrix flops / peak of the pipe they run on,
+always <= 1; algorithmic-equivalent rates in their own keys).
+
+A plain run does only that: set up, warm up, time the --steps steps, print the line.  `--full` adds what needs work of its
+own, all outside the timed region: `configs1_corr_only` (the round-1 headline, kept as a sub-record), `conv_error_vs_fp64`,
+`power_probe`, the `value_*` passes on the other convolution arithmetics (unless --no-alt), and `cpu_baseline` (the same
+forward on the host cores through oracle/cpu_chain.py, with the GPU-vs-CPU parity of three pairs of the timed batch and
+`parity_ok`, unless --no-cpu-baseline).
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its last step as DIR/<name>.npy
+(float32; integer maps as float64), under 64 MB in all: see dump_outputs().  Inputs and weights are seeded, so two runs with
+the same arguments see the same inputs and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -426,6 +435,48 @@ def cpu_baseline_corr(h, C, budget_s=12.0):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000    # all files of one dump together (npy headers included) stay under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(d, arrays, budget=DUMP_BUDGET_BYTES):
+    """{name: tensor} -> d/<name>.npy: floating tensors as float32 (float64 stays float64), integer maps as float64 (exact).
+    Arrays are written smallest first; each may take an equal share of what the budget has left.  One that does not fit is
+    replaced by a fixed sample: seeded-random slices along its leading dimension (whole images / maps, in ascending order)
+    if one slice fits, else every k-th element of the flattened array from a seeded start.  Returns {name: what was
+    written} for the log."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left, info = budget, {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t.double() if not t.is_floating_point() or t.dtype == torch.float64 else t.float()
+        share = left // (len(items) - i) - 128                   # 128: the npy header
+        what = {"shape": list(t.shape)}
+        if t.numel() * t.element_size() > share:
+            per = t[0].numel() * t.element_size() if t.dim() > 1 else share + 1
+            if per <= share:
+                rows = np.sort(rng.choice(t.shape[0], share // per, replace=False))
+                t = t[torch.from_numpy(rows).to(t.device)]
+                what["sampled_rows"] = rows.tolist()
+            else:
+                step = -(-t.numel() // max(1, share // t.element_size()))
+                start = int(rng.integers(step))
+                t = t.reshape(-1)[start::step]
+                what["sampled_flat"] = {"start": start, "step": step}
+        a = np.ascontiguousarray(t.cpu().numpy())
+        np.save(os.path.join(d, f"{name}.npy"), a)
+        left -= a.nbytes + 128
+        info[name] = dict(what, written=list(a.shape), dtype=str(a.dtype))
+    return info
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -441,12 +492,18 @@ def main():
     ap.add_argument("--graph", choices=("0", "1"), default="0",
                     help="train workload: capture the training step into a hipGraph (train.hip_graph; one process only).  Measured on "
                          "configs[3]: 33.1 ms against 31.7 ms eager -- the step is GPU-bound, not launch-bound -- hence off by default")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra passes on the other convolution arithmetics")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check what needs work outside the timed steps: configs[1] sub-record, convolution error "
+                         "vs fp64, power probe, the other convolution arithmetics, CPU baseline + GPU-vs-CPU parity (exit code)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, under 64 MB in all: a fixed seeded sample of larger outputs)")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the extra passes on the other convolution arithmetics")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="bf16: inference under torch.autocast(bfloat16) (configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--experimental", action="store_true",
-                    help="also time the step on the Winograd-along-y kernels of csrc/experimental/ (a library built with `make "
-                         "EXPERIMENTAL=1`; round 5's recorded no-go, DESIGN.md 6.7)")
+                    help="--full: also time the step on the Winograd-along-y kernels of csrc/experimental/ (a library built with "
+                         "`make EXPERIMENTAL=1`; round 5's recorded no-go, DESIGN.md 6.7)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch-path check without a GPU workload: respawn under torch.distributed.run, read RANK / LOCAL_RANK / "
                          "WORLD_SIZE, init the process group ($C2M_BENCH_BACKEND, default nccl = RCCL; gloo on a CPU-only host), "
@@ -553,6 +610,11 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
 
+    def dump(arrays):   # rank 0's outputs of the last timed step, before anything else runs on the device
+        if args.dump_outputs and rank == 0:
+            info = dump_outputs(args.dump_outputs, arrays)
+            print(f"bench.py: --dump-outputs {args.dump_outputs}: {json.dumps(info)}", file=sys.stderr)
+
     # HBM bytes from the PMC passes kept under profiles/ (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate runs of this very
     # command; gfx950 corrections applied by scripts/summarize_step.py).  STATIC: measured once per round on the default
     # workload, not during this run -- `traffic_source` says so in the line
@@ -607,6 +669,7 @@ def main():
             return model.log_dict["l_g_pix"]
 
         dt, kern, loss = timed(train_step)
+        dump({"loss": torch.as_tensor(loss).reshape(1), "sr": model.output})
         grad_bytes = sum(p.numel() * 4 for p in unwrap(model.net_g).parameters() if p.requires_grad)
         line = dict(base, metric=METRIC + " -- stage-3 training step", value=_rnd(B * world * args.steps / dt, 3),
                     ms_per_step=_rnd(dt / args.steps * 1e3, 3), dtype="f32", scaling="strong" if args.batch is None else "weak",
@@ -635,6 +698,8 @@ def main():
 
     if args.workload == "corr":
         dt, kern, out = timed(corr_step)
+        dump({"index_map": out[0], "max_val": out[1], "pre_offset_s1": out[2][0], "pre_offset_s2": out[2][1],
+              "pre_offset_s4": out[2][2]})
         assert int(out[0].min()) >= 0 and int(out[0].max()) < (h - 2) ** 2
         swept = corr_swept_rows(h)
         ck = kern.get("corr_argmax_mfma", [])
@@ -648,7 +713,7 @@ def main():
                     corr_roofline(B, C, h, sum(ck) / max(len(ck), 1), len(ck), pmc, swept))
         line["c2m_kernel_ms_per_step"] = {k: round(sum(v) / args.steps, 4) for k, v in kern.items()}
         line["rank_step_ms"] = timed.rank_step_ms
-        if world == 1 and not args.no_cpu_baseline and rank == 0:
+        if args.full and world == 1 and not args.no_cpu_baseline and rank == 0:
             line["cpu_baseline"] = cpu_baseline_corr(h, C)
         return finish(line)
 
@@ -687,6 +752,7 @@ def main():
         return whole()
 
     dt, kern, sr = timed(restore_step)
+    dump({"sr": sr})
     rank_ms = timed.rank_step_ms
     pre_timed = last["pre"]     # (the extra passes on other arithmetics below overwrite last["pre"])
     fam = timed.families
@@ -698,7 +764,7 @@ def main():
             stage[name] += e[k].elapsed_time(e[k + 1]) / args.steps
 
     sub = None
-    if rank == 0 and dist is None and h == 160 and not bf16:   # configs[1] sub-record (short: 3 steps)
+    if args.full and rank == 0 and dist is None and h == 160 and not bf16:   # configs[1] sub-record (short: 3 steps)
         steps_keep, args.steps = args.steps, 3
         sdt, skern, _ = timed(corr_step)
         args.steps = steps_keep
@@ -748,7 +814,7 @@ def main():
                     stage_ms={k: _rnd(v, 2) for k, v in stage.items()}, kernel_table=table, roofline=dominant,
                     c2m_kernel_ms_per_step={k: _rnd(sum(v) / args.steps, 3) for k, v in kern.items()},
                     configs1_corr_only=sub, notes="profiles/bench_notes.md", rank_step_ms=rank_ms)
-        if not bf16:
+        if args.full and not bf16:
             try:   # measured, on this GPU, in this run: distance of every convolution arithmetic from a float64 convolution
                 g_ = torch.Generator(device=dev).manual_seed(77)
                 xe = torch.randn((1, 256, 24, 64), generator=g_, device=dev).contiguous(memory_format=torch.channels_last)
@@ -811,7 +877,7 @@ def main():
                             _ops._WINO16 = keep_w
                 finally:
                     _ops._SPLIT16, _ops._SPLIT = keep
-        if world == 1 and not args.no_cpu_baseline and not bf16:
+        if args.full and world == 1 and not args.no_cpu_baseline and not bf16:
             idx_gpu = pre_timed.max_idx.cpu().numpy()
             line["cpu_baseline"] = cpu_baseline_restore(ext, mp, net, lq, up, ref, sr, idx_gpu)
             # north_star's tolerance as an ASSERTION of the run: given the GPU's own index map the SR image must

@@ -40,10 +40,10 @@ for stage in "$@"; do
     test_rest)  timeout 1500 python -m pytest tests/test_restoration_gpu.py -m gpu -q -rA 2>&1 | tail -80 > $O/pytest_restoration.log ;;
     test_all)   timeout 2400 python -m pytest tests -m gpu -q -rA 2>&1 | tail -220 > $O/pytest_gpu.log ;;
     diag_corr)  timeout 600 python scripts/diag_corr_filter.py --lr320 > $O/diag_corr_filter.log 2>&1 ;;
-    bench)      timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.log 2>&1; echo "rc=$?" >> $O/bench_default.log ;;
+    bench)      timeout 900 python bench.py --steps 20 --warmup 5 --full > $O/bench_default.log 2>&1; echo "rc=$?" >> $O/bench_default.log ;;
     bench_dist1) C2M_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-alt > $O/bench_dist1.log 2>&1; echo "rc=$?" >> $O/bench_dist1.log ;;
     bench_quick) timeout 600 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-alt > $O/bench_quick.log 2>&1; echo "rc=$?" >> $O/bench_quick.log ;;
-    bench_corr) timeout 300 python bench.py --workload corr --steps 10 --warmup 3 > $O/bench_corr.log 2>&1 ;;
+    bench_corr) timeout 300 python bench.py --workload corr --steps 10 --warmup 3 --full > $O/bench_corr.log 2>&1 ;;
     bench_train) timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $O/bench_train.log 2>&1
                 C2M_TRAIN_KERNELS=0 timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $O/bench_train_stock.log 2>&1
                 timeout 300 python bench.py --workload train --batch 4 --steps 20 --warmup 5 > $O/bench_train_b4.log 2>&1
@@ -51,7 +51,7 @@ for stage in "$@"; do
                 C2M_TRAIN_KERNELS=1 timeout 300 python bench.py --workload train --steps 20 --warmup 5 > $O/bench_train_kernels.log 2>&1
                 C2M_BENCH_FORCE_DIST=1 timeout 300 python bench.py --workload train --steps 10 --warmup 3 > $O/bench_train_rccl_1rank.log 2>&1 ;;
     bench_cfg5) timeout 300 python bench.py --lr 320 --dtype bf16 --steps 5 --warmup 2 > $O/bench_cfg5_bf16.log 2>&1
-                timeout 300 python bench.py --lr 320 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg5_f32.log 2>&1 ;;
+                timeout 300 python bench.py --lr 320 --steps 5 --warmup 2 --full --no-cpu-baseline > $O/bench_cfg5_f32.log 2>&1 ;;
     bench_cfg5_bf16) timeout 300 python bench.py --lr 320 --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg5_bf16.log 2>&1
                 C2M_BF16_IO=0 timeout 300 python bench.py --lr 320 --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_cfg5_bf16_f32io.log 2>&1 ;;
     bench_conv16) (echo "== bf16 kernel, fp32 tensors, B=4"; timeout 200 python scripts/bench_conv.py --batch 4 --algo bf16 --only body

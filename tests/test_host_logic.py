@@ -191,6 +191,40 @@ def test_bench_power_probe_parses_rocm_smi_and_never_raises(monkeypatch, tmp_pat
     assert "error" in got, got
 
 
+def test_bench_dump_outputs_fits_the_budget_and_samples_the_same_way_every_time(tmp_path):
+    """bench.py --dump-outputs: floating outputs land as float32, integer maps as float64 (exact), small arrays whole, the whole
+    dump under 64 MB, and the sample of an oversized output is the same
+    from run to run (two builds are compared file for file)."""
+    import importlib.util
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"index_map": torch.randint(0, 158 * 158, (16, 158, 158), generator=g),
+              "max_val": torch.rand((16, 158, 158), generator=g),
+              "sr": torch.rand((16, 3, 640, 640), generator=g).to(torch.bfloat16),
+              "pre_offset_s4": torch.rand((2, 9, 640, 640, 2), generator=g)}
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        info = bench.dump_outputs(str(d), arrays)
+        files = sorted(os.listdir(d))
+        assert files == sorted(f"{n}.npy" for n in arrays)
+        assert sum(os.path.getsize(d / f) for f in files) < 64 * 10 ** 6
+        runs.append({f: np.load(d / f) for f in files})
+    a = runs[0]
+    assert a["index_map.npy"].dtype == np.float64 and np.array_equal(a["index_map.npy"], arrays["index_map"].numpy())
+    assert a["max_val.npy"].dtype == np.float32 and np.array_equal(a["max_val.npy"], arrays["max_val"].numpy())
+    rows = info["sr"]["sampled_rows"]                      # whole images of the batch, in ascending order
+    assert a["sr.npy"].dtype == np.float32 and a["sr.npy"].shape == (len(rows), 3, 640, 640) and rows == sorted(rows)
+    assert np.array_equal(a["sr.npy"], arrays["sr"][rows].float().numpy())
+    s = info["pre_offset_s4"]["sampled_flat"]               # one image is larger than its share: every k-th element
+    assert np.array_equal(a["pre_offset_s4.npy"], arrays["pre_offset_s4"].reshape(-1)[s["start"]::s["step"]].numpy())
+    assert all(np.array_equal(runs[0][f], runs[1][f]) for f in runs[0])
+
+
 def test_bench_dcn_roofline_prices_both_gemm_arithmetics():
     """bench.py's DCNv2 rows: the fp32 GEMM executes the algorithmic flops on the fp32 matrix pipe; the f16 x 2 GEMM executes
     three products per k step on the f16 pipe -- `frac` is always executed / that pipe's dense peak, and `frac_vs_fp32_pipe`
