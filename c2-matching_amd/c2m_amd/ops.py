@@ -428,8 +428,6 @@ class _WeightCache:
             self._d.clear()
             self._tables.clear()
 
-    _SPLIT_PIECES = {3: 3, 4: 1, 5: 3, 6: 2, 7: 0x42, 8: 0x22}     # cache kind -> pieces code of the split-kernel image (7 / 8: Winograd F(4,3) / F(2,3) along y on f16 x 2)
-
     def refresh(self, param_ids=None, kinds=None):
         with self._lock:
             return self._refresh_locked(param_ids, kinds)
@@ -451,12 +449,12 @@ class _WeightCache:
             rows, kind = (slot[1], slot[2]) if isinstance(slot, tuple) and len(slot) == 3 else (None, None)
             if kinds is not None and kind is not None and kind not in kinds:
                 continue
-            if kind in self._SPLIT_PIECES and len(key) == 5 and key[3] is None and w.is_contiguous() and (dev is None or dev == w.device):
+            pieces = _KINDS[kind].pieces if isinstance(kind, int) else 0   # (the DCN cache's slots are not conv3x3 kinds)
+            if pieces and len(key) == 5 and key[3] is None and w.is_contiguous() and (dev is None or dev == w.device):
                 dev = w.device
                 Co, Ci = (rows[1] - rows[0] if rows is not None else w.shape[0]), w.shape[1]
                 cin_k, cout_k = (Co, Ci) if kind == 5 else (Ci, Co)      # the data-gradient conv swaps the roles
-                pieces = self._SPLIT_PIECES[kind]
-                nbytes = _lib.lib().c2m_conv3x3_relayout_split_bytes(cin_k, cout_k, pieces) - (256 if (pieces & 15) == 2 else 0)
+                nbytes = _lib.lib().c2m_conv3x3_relayout_split_bytes(cin_k, cout_k, pieces) - (256 if pieces == 2 else 0)
                 wptr = w.data_ptr() + (rows[0] * Ci * 9 * 4 if rows is not None else 0)
                 jobs.append((wptr, value.data_ptr(), cin_k, cout_k, pieces | ((1 if cout_k <= 32 else 2) << 8) | ((1 if kind == 5 else 0) << 16),
                              nbytes // 2))
@@ -487,7 +485,7 @@ class _WeightCache:
         return n
 
     @staticmethod
-    def _relayout(weight, rows, pad_cin_to, wino, wr=None):
+    def _relayout(weight, rows, pad_cin_to, kind, wr=None):
         w = weight.detach()
         if rows is not None:
             w = w[rows[0]:rows[1]]
@@ -499,38 +497,38 @@ class _WeightCache:
             Ci = pad_cin_to
         w = w.contiguous()
         L = _lib.lib()
-        wino = int(wino)
-        if wino in (3, 4, 5, 6, 7, 8):   # split images (3 exact bf16 pieces / 1 rounded piece per weight; 6: scaled f16 x 2; 7 / 8: its Winograd-along-y images); 5: of the data-gradient conv
-            pieces = 1 if wino == 4 else 2 if wino == 6 else 0x42 if wino == 7 else 0x22 if wino == 8 else 3
-            nbytes = L.c2m_conv3x3_relayout_split_bytes(Co, Ci, pieces) if wino == 5 else L.c2m_conv3x3_relayout_split_bytes(Ci, Co, pieces)
+        kind = int(kind)
+        pieces = _KINDS[kind].pieces
+        if pieces:   # split images (3 exact bf16 pieces / 1 rounded piece per weight / scaled f16 x 2); kind 5: of the data-gradient conv
+            nbytes = L.c2m_conv3x3_relayout_split_bytes(Co, Ci, pieces) if kind == 5 else L.c2m_conv3x3_relayout_split_bytes(Ci, Co, pieces)
         else:
-            nbytes = (L.c2m_conv3x3_relayout_bytes, L.c2m_conv3x3_relayout_wino_bytes, L.c2m_conv3x3_relayout_wino4_bytes)[wino](Ci, Co)
+            nbytes = (L.c2m_conv3x3_relayout_bytes, L.c2m_conv3x3_relayout_wino_bytes, L.c2m_conv3x3_relayout_wino4_bytes)[kind](Ci, Co)
         if nbytes == 0:
-            raise _lib.C2MError(f"conv3x3: unsupported channel counts Cin={Ci}, Cout={Co}" + (" for this kernel" if wino else
+            raise _lib.C2MError(f"conv3x3: unsupported channel counts Cin={Ci}, Cout={Co}" + (" for this kernel" if kind else
                                 " (input channels must be a multiple of 32)"))
         if wr is None:
             wr = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=w.device)
         with torch.cuda.device(w.device):
-            if wino == 5:
+            if kind == 5:
                 _lib.check(L.c2m_conv3x3_relayout_split_dgrad_f32(_stream(), w.data_ptr(), Ci, Co, pieces, wr.data_ptr()),
                            "c2m_conv3x3_relayout_split_dgrad_f32")
-            elif wino in (3, 4, 6, 7, 8):
+            elif pieces:
                 _lib.check(L.c2m_conv3x3_relayout_split_f32(_stream(), w.data_ptr(), Ci, Co, pieces, wr.data_ptr()),
                            "c2m_conv3x3_relayout_split_f32")
             else:
-                fn = (L.c2m_conv3x3_relayout_f32, L.c2m_conv3x3_relayout_wino_f32, L.c2m_conv3x3_relayout_wino4_f32)[wino]
+                fn = (L.c2m_conv3x3_relayout_f32, L.c2m_conv3x3_relayout_wino_f32, L.c2m_conv3x3_relayout_wino4_f32)[kind]
                 _lib.check(fn(_stream(), w.data_ptr(), Ci, Co, wr.data_ptr()), "c2m_conv3x3_relayout")
         return wr
 
-    def get(self, weight, pad_cin_to=None, rows=None, wino=0):   # wino: 0 direct, 1 F(2,3), 2 F(4,3), 3 split-bf16x3, 4 bf16, 5 dgrad, 6 split-f16x2
+    def get(self, weight, pad_cin_to=None, rows=None, kind=0):   # kind: a row of _KINDS
         key = (weight.data_ptr(), weight._version, tuple(weight.shape), pad_cin_to, weight.device.index)
-        slot = (id(weight), rows, wino)
+        slot = (id(weight), rows, kind)
         hit = self._lookup(slot, key, weight)
         if hit is not None:
             return hit
-        wr = self._relayout(weight, rows, pad_cin_to, wino)
+        wr = self._relayout(weight, rows, pad_cin_to, kind)
         self._store(slot, key, weight, wr,
-                    redo=lambda w, buf, rows=rows, pad=pad_cin_to, wino=wino: self._relayout(w, rows, pad, wino, buf))
+                    redo=lambda w, buf, rows=rows, pad=pad_cin_to, kind=kind: self._relayout(w, rows, pad, kind, buf))
         return wr
 
 
@@ -552,6 +550,7 @@ def empty_nhwc(B, C, H, W, device, dtype=torch.float32):
     return torch.empty((B, C, H, W), dtype=dtype, device=device, memory_format=torch.channels_last)
 
 
+import collections as _collections
 import os as _os
 
 _WINO = _os.environ.get("C2M_CONV_WINO", "1") != "0"
@@ -566,38 +565,27 @@ _SPLIT = _os.environ.get("C2M_CONV_SPLIT", "all")
 # domain |x| < 65520: include/c2m_hip.h C2M_CONV_SPLIT_F16X2); "0" -- the bf16 x 3 flavour (full fp32 range) everywhere.
 # The autograd path (conv3x3_autograd: gradients can be tiny) always runs bf16 x 3.
 _SPLIT16 = _os.environ.get("C2M_CONV_SPLIT16", "1") != "0"
-# C2M_CONV_WINO16: "0" (default) off; "43" / "23" -- where the f16 x 2 flavour would run a channels-last layer with Cout % 64 == 0 it
-# runs behind a Winograd F(4,3) / F(2,3) transform ALONG Y (csrc/conv3x3_wino16.hip: 1/2 / 2/3 of the matrix instructions).  Measured
-# (round 5): F(4,3) is 6 % faster than the direct f16 x 2 kernel on 64 -> 64 @640^2 and 2-2.5x further from float64
-# than the exact-fp32 kernel on 64-channel layers; F(2,3) is more accurate than the direct kernel and 12 % slower -- the family is
-# bound by vector-memory traffic, not by the matrix pipe.  Not the default; algo="wino16" / "wino16_f23" select it per call.
-# Round 6: the kernel lives in csrc/experimental/ and is only in a library built with `make EXPERIMENTAL=1` (experimental_built()).
-_WINO16 = {"43": 7, "23": 8}.get(_os.environ.get("C2M_CONV_WINO16", "0"), 0)
 
 
 def experimental_built():
-    """True if libc2m_hip.so was built with `make EXPERIMENTAL=1` (csrc/experimental/: the Winograd-along-y and loader /
-    matrix-wave convolution kernels, both measured no-gos kept for their numbers -- DESIGN.md 6.7, 6.10).  Probed once by a
-    one-tile launch: the product library answers algo "wino16" with C2M_ERR_UNSUPPORTED."""
-    v = getattr(experimental_built, "_v", None)
-    if v is None:
-        x = torch.zeros((1, 16, 4, 32), device="cuda").contiguous(memory_format=torch.channels_last)
-        try:
-            conv3x3(x, torch.zeros((64, 16, 3, 3), device="cuda"), algo="wino16_f23")
-            v = True
-        except _lib.C2MError:
-            v = False
-        experimental_built._v = v
-    return v
+    """Always False: the experimental conv kernels (measured no-gos) were removed from the source."""
+    return False
+
+
 # C2M_DCN_F16X2: "1" (default) -- the DCNv2 forward's implicit GEMM follows the convolutions onto the f16 x 2 arithmetic
 _DCN_F16X2 = _os.environ.get("C2M_DCN_F16X2", "1") != "0"
-# internal kernel ids (= weight-cache kinds; 5 is the data-gradient image of the bf16 x 3 kernel) -> c2m_conv3x3_desc.algo
-ALGO_IDS = {"direct": 0, "winograd": 1, "winograd4": 2, "split": 3, "bf16": 4, "split16": 6, "wino16": 7, "wino16_f23": 8}
-_DESC_ALGO = (0, 1, 2, 3, 4, 3, 5, 6, 7)
-_FAMILY = ("direct", "winograd_f23", "winograd_f43", "split_bf16x3", "bf16", "split_bf16x3", "split_f16x2", "wino16_f43y", "wino16_f23y")
-# matrix flops actually executed per algorithmic (direct-convolution) flop, and the pipe they run on (Winograd along y on
-# f16 x 2: three products x 6/12 (4/6) of the taps x 32/30 of the columns -- two MFMA columns of a tile are halo only)
-_EXEC_FACTOR = (1.0, 2.0 / 3.0, 0.5, 6.0, 1.0, 6.0, 3.0, 3.0 * 0.5 * 32.0 / 30.0, 3.0 * (2.0 / 3.0) * 32.0 / 30.0)
+# conv3x3 kernel kinds (= weight-cache slot keys), one row each: public algo= name (kind 5, the data-gradient image of the
+# bf16 x 3 kernel, has none), c2m_conv3x3_desc.algo, family name of the flop counters (conv_flops_by_family), matrix flops
+# executed per algorithmic (direct-convolution) flop, pieces of its c2m_conv3x3_relayout_split_f32 image (0: not a split image)
+_Kind = _collections.namedtuple("_Kind", "name algo family exec_factor pieces")
+_KINDS = (_Kind("direct", 0, "direct", 1.0, 0),
+          _Kind("winograd", 1, "winograd_f23", 2.0 / 3.0, 0),
+          _Kind("winograd4", 2, "winograd_f43", 0.5, 0),
+          _Kind("split", 3, "split_bf16x3", 6.0, 3),
+          _Kind("bf16", 4, "bf16", 1.0, 1),
+          _Kind(None, 3, "split_bf16x3", 6.0, 3),
+          _Kind("split16", 5, "split_f16x2", 3.0, 2))
+ALGO_IDS = {k.name: i for i, k in enumerate(_KINDS) if k.name}
 
 
 # ---- f16 x 2 is the DEFAULT arithmetic of fp32 inference, and its domain is |activation| < 65520: outside it the kernel
@@ -790,21 +778,20 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
         reduced = bf16_autocast()
         if (out2_grouped8 is None and (_split_ok(srcs, weight, fast) or (reduced and _split_ok(srcs, weight, True))) and (out_mode != "nhwc_pool2" or (H % 2 == 0 and W % 2 == 0))
                 and (out_mode not in ("nhwc", "nhwc_pool2") or Cout % 4 == 0)):   # channels-last stores are 16-byte vectors
-            wino = 4 if reduced else 6 if _f16x2_auto() else 3
-            if (wino == 6 and _WINO16 and out_mode == "nhwc" and Cout % 64 == 0 and out is None and out_dtype in (None, torch.float32)
-                    and all(t_ is None or t_.dtype == torch.float32 for t_ in (srcs[0], res1, res2))):
-                wino = _WINO16
+            kind = 4 if reduced else 6 if _f16x2_auto() else 3
         else:
-            wino = 2 if (fast and _wino4_ok(srcs, weight, out_mode, W)) else 1 if _wino_ok(srcs, weight, out_mode, W) else 0
+            kind = 2 if (fast and _wino4_ok(srcs, weight, out_mode, W)) else 1 if _wino_ok(srcs, weight, out_mode, W) else 0
+    elif algo in ALGO_IDS:
+        kind = ALGO_IDS[algo]
     else:
-        wino = ALGO_IDS[algo]
+        raise _lib.C2MError(f"conv3x3: unknown algo {algo!r} (one of {', '.join(ALGO_IDS)})")
     if out2_grouped8 is not None:
         if algo not in (None, "direct") or out_mode != "nhwc":
             raise _lib.C2MError("out2_grouped8 needs the direct kernel in nhwc mode")
-        wino = 0
-    wr = _wcache.get(weight, pad_cin_to=Cin if weight.shape[1] < Cin else None, wino=wino)
+        kind = 0
+    wr = _wcache.get(weight, pad_cin_to=Cin if weight.shape[1] < Cin else None, kind=kind)
     d = _lib.Conv3x3Desc()
-    d.algo = _DESC_ALGO[wino]
+    d.algo = _KINDS[kind].algo
     d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cin, Cout, len(srcs)
     for k, s in enumerate(srcs):
         if tuple(s.shape[2:]) != (H, W) or s.shape[0] != B:
@@ -822,10 +809,10 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     for bit, r in ((4, res1), (8, res2)):
         if r is not None and r.dtype == torch.bfloat16:
             io |= bit
-    if io and (wino != 4 or out_mode != "nhwc"):
+    if io and (kind != 4 or out_mode != "nhwc"):
         raise _lib.C2MError("conv3x3: bfloat16 tensors need the bf16 kernel (algo='bf16' / bf16 autocast) in nhwc mode")
     if dword_stores:
-        if io or wino not in (3, 4, 6) or out_mode not in ("pixel_shuffle", "nchw"):
+        if io or kind not in (3, 4, 6) or out_mode not in ("pixel_shuffle", "nchw"):
             raise _lib.C2MError("conv3x3: dword_stores selects a store path of the split kernels' pixel_shuffle / nchw epilogues")
         io = 16
     d.io_flags = io
@@ -854,7 +841,7 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
         o = _nhwc_src(out, "out")
         d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = o.pix_pitch, o.row_pitch, o.img_pitch
     elif out_mode == "nhwc_pool2":
-        if wino not in (1, 3, 4, 6) or H % 2 != 0 or W % 2 != 0:
+        if kind not in (1, 3, 4, 6) or H % 2 != 0 or W % 2 != 0:
             raise _lib.C2MError("conv3x3: the pooled epilogue needs the Winograd F(2,3) or the split-bf16 kernel and even H, W")
         out = empty_nhwc(B, Cout, H // 2, W // 2, dev)
         d.out_mode = 4
@@ -866,76 +853,13 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     else:
         raise _lib.C2MError(f"unknown out_mode {out_mode}")
     d.out = out.data_ptr()
-    if wino in (6, 7, 8):
+    if kind == 6:
         d.range_flag = _range_flag(dev).data_ptr()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
     if _ConvFlops.enabled:
-        _ConvFlops.add(_FAMILY[wino], 2.0 * Cout * 9 * Cin * H * W * B, 2.0 * Cout * 9 * Cin * H * W * B * _EXEC_FACTOR[wino])
-    return out
-
-
-# C2M_RESBLOCK: "0" (default) -- a ResidualBlockNoBN (arch_util.py:80-136) is two conv3x3 launches; "1" -- the fused inference
-# bodies run it as ONE launch (csrc/experimental/conv3x3_resblock.hip: the intermediate tensor stays in LDS) on maps of at least
-# C2M_RESBLOCK_MINPIX pixels, IF the library was built with `make EXPERIMENTAL=1`.  Round 6 built and measured it:
-# right on its first run on hardware, equal to the two-launch path to 1 ulp -- and 6 - 7 % SLOWER at 640^2 / 320^2, 25 % at 160^2
-# (on this chip a wave's vector-ALU instructions are paid for in matrix-pipe time whether or not another wave
-# runs beside it, and the fused form needs 11 % more MFMAs plus more vector work per MFMA).  A recorded no-go, kept for its numbers.
-_RESBLOCK = _os.environ.get("C2M_RESBLOCK", "0")
-_RESBLOCK_MINPIX = int(_os.environ.get("C2M_RESBLOCK_MINPIX", str(300 * 300)))
-
-
-def resblock3x3_ok(x, w1, w2, res2=None):
-    """True if `resblock3x3` takes these tensors: fp32 channels-last GPU activations, two [64, 64, 3, 3] weights."""
-    return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 64 and x.stride(1) == 1 and
-            tuple(w1.shape) == (64, 64, 3, 3) and tuple(w2.shape) == (64, 64, 3, 3) and
-            (res2 is None or (res2.dtype == torch.float32 and res2.shape == x.shape and res2.stride() == x.stride())))
-
-
-def resblock3x3_wanted(x):
-    """The policy of the fused bodies (ref_restoration_arch._fused_body): f16 x 2 active for this thread's auto calls, map large enough."""
-    if _RESBLOCK != "1" or _SPLIT == "0" or not _f16x2_auto():
-        return False
-    return x.shape[2] * x.shape[3] >= _RESBLOCK_MINPIX and bool(_lib.lib().c2m_resblock3x3_supported(64, x.shape[2], x.shape[3]))
-
-
-def resblock3x3(x, w1, b1, w2, b2, res2=None, out=None):
-    """out = x + conv2(relu(conv1(x) + b1)) + b2 (+ res2): a ResidualBlockNoBN (arch_util.py:128-136, res_scale 1) in ONE launch
-    on the f16 x 2 arithmetic (c2m_resblock3x3_nhwc_f32: the intermediate tensor stays in LDS, x is read once, the identity is
-    rebuilt from x's two f16 pieces -- equal to two conv3x3(algo="split16") launches up to that rounding, |d| <= 2^-22 |x|).
-    Needs a library built with `make EXPERIMENTAL=1` (C2MError "unsupported" otherwise): a measured no-go, see _RESBLOCK above.
-    x: channels_last [B,64,H,W] fp32; domain as algo="split16" (range flag of the enclosing guard / the device)."""
-    if not resblock3x3_ok(x, w1, w2, res2):
-        raise _lib.C2MError("resblock3x3: channels_last float32 GPU tensor [B,64,H,W], weights [64,64,3,3]")
-    B, _, H, W = x.shape
-    dev = x.device
-    wr1, wr2 = _wcache.get(w1, wino=6), _wcache.get(w2, wino=6)
-    if out is None:
-        out = empty_nhwc(B, 64, H, W, dev)
-    if out.data_ptr() == x.data_ptr():
-        raise _lib.C2MError("resblock3x3: out may not alias x")
-    xs, o = _nhwc_src(x, "x"), _nhwc_src(out, "out")
-    d = _lib.ResBlockDesc()
-    d.B, d.H, d.W, d.C = B, H, W, 64
-    d.x, d.x_pix_pitch, d.x_row_pitch, d.x_img_pitch = xs.ptr, xs.pix_pitch, xs.row_pitch, xs.img_pitch
-    d.out, d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch
-    if res2 is not None:
-        r = _nhwc_src(res2, "res2")
-        if (r.pix_pitch, r.row_pitch, r.img_pitch) != (o.pix_pitch, o.row_pitch, o.img_pitch):
-            raise _lib.C2MError("resblock3x3: res2 must have the geometry of the output")
-        d.res2 = res2.data_ptr()
-    d.wr1, d.wr2 = wr1.data_ptr(), wr2.data_ptr()
-    b1 = _dev_f32(b1.detach(), "bias1") if b1 is not None else None
-    b2 = _dev_f32(b2.detach(), "bias2") if b2 is not None else None
-    d.bias1 = b1.data_ptr() if b1 is not None else None
-    d.bias2 = b2.data_ptr() if b2 is not None else None
-    d.range_flag = _range_flag(dev).data_ptr()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().c2m_resblock3x3_nhwc_f32(_stream(), d), "c2m_resblock3x3_nhwc_f32")
-    if _ConvFlops.enabled:
-        alg = 2 * 2.0 * 64 * 9 * 64 * H * W * B
-        steps = B * ((W + 29) // 30) * ((H + 2 + 7) // 8)          # strips x steps of 8 rows x 32 MFMA columns, both convolutions
-        _ConvFlops.add("resblock_split_f16x2", alg, steps * 2 * 3.0 * 2.0 * 64 * 9 * 64 * 256)
+        f = 2.0 * Cout * 9 * Cin * H * W * B
+        _ConvFlops.add(_KINDS[kind].family, f, f * _KINDS[kind].exec_factor)
     return out
 
 
@@ -946,10 +870,10 @@ def conv3x3_dgrad(grad_out, weight):
     B, Cg, H, W = grad_out.shape
     if Cg != Cout or Cout % 16 != 0 or Cin % 4 != 0:
         raise _lib.C2MError("conv3x3_dgrad: grad_out channels must equal weight.shape[0] (a multiple of 16); Cin % 4 == 0")
-    wr = _wcache.get(weight, wino=5)
+    wr = _wcache.get(weight, kind=5)
     out = empty_nhwc(B, Cin, H, W, grad_out.device)
     d = _lib.Conv3x3Desc()
-    d.algo = 3
+    d.algo = _KINDS[5].algo
     d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cout, Cin, 1
     d.src[0] = _nhwc_src(grad_out, "grad_out")
     d.wr = wr.data_ptr()
@@ -1066,24 +990,19 @@ def conv3x3_rgb64(image, weight, bias=None, act=ACT_NONE, slope=0.1, mean=None, 
     """First layer of an image tower (3 -> 64 channels; vgg conv1_1, conv_first) as its own im2col kernel:
     out = act(conv3x3((image - mean) / std) + bias), channels_last [B,64,H,W].  image: [B,3,H,W] (any layout; read as
     contiguous NCHW); mean / std: [1,3,1,1] buffers of the extractor or None.  out / out2_grouped8 as in conv3x3."""
-    x = image.float().contiguous()
-    if x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+    if image.dim() != 4 or image.shape[1] != 3 or not image.is_cuda:
         raise _lib.C2MError("conv3x3_rgb64: image must be a GPU tensor [B,3,H,W]")
     if tuple(weight.shape) != (64, 3, 3, 3):
         raise _lib.C2MError("conv3x3_rgb64: weight must be [64,3,3,3]")
-    B, _, H, W = x.shape
-    dev = x.device
+    B, _, H, W = image.shape
     if (mean is None) != (std is None):
         raise _lib.C2MError("conv3x3_rgb64: mean and std go together")
-    if 12 * H * W >= 2 ** 31 and out2_grouped8 is None:
-        # the first-layer kernel addresses one image with 32-bit buffer offsets (12 bytes per pixel: H * W < 178 956 971, e.g.
-        # 13 377 x 13 377); beyond that the layer runs on the generic kernel over a 32-channel zero-padded copy (what
-        # ContentExtractor.forward_fused does for first layers that are not 3 -> 64) instead of raising (ADVICE r5)
-        xn = x if mean is None else (x - mean.detach().reshape(1, 3, 1, 1).float()) / std.detach().reshape(1, 3, 1, 1).float()
-        x32 = torch.zeros((B, 32, H, W), dtype=torch.float32, device=dev).contiguous(memory_format=torch.channels_last)
-        x32[:, :3] = xn
-        with conv_flavour("bf16x3"):   # (explicitly full range: no guard needed, no f16 x 2 domain question)
-            return conv3x3(x32, weight, bias, act=act, slope=slope, out=out)
+    if 12 * H * W >= 2 ** 31:
+        # checked before anything is copied: the kernel addresses one image with 32-bit byte offsets (12 bytes per pixel), and
+        # the generic kernel on a 32-channel padded copy has the same 2^31-byte bound per sample at a tenth of the pixels
+        raise _lib.C2MError(f"conv3x3_rgb64: image of {H} x {W} pixels is too large (H * W < 178 956 971)")
+    x = image.float().contiguous()
+    dev = x.device
     w = _dev_f32(weight.detach(), "weight")
     bias = _dev_f32(bias.detach(), "bias") if bias is not None else None
     if mean is not None:
@@ -1149,12 +1068,12 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
     for (c0, c1) in slices:
         # split-bf16 kernel (any shape); else 64-channel-tileable slices on whole 32-pixel tiles take the Winograd F(2,3)
         # kernel (1.5x fewer matrix instructions), the rest the direct kernel
-        wino = split_id if use_split else int(_WINO and algo is None and (c1 - c0) % 64 == 0 and W % 32 == 0 and
+        kind = split_id if use_split else int(_WINO and algo is None and (c1 - c0) % 64 == 0 and W % 32 == 0 and
                                        all(s_.shape[1] % 16 == 0 for s_ in srcs))
-        fam.append(wino)
-        wr = _wcache.get(weight, rows=(c0, c1), wino=wino)
+        fam.append(kind)
+        wr = _wcache.get(weight, rows=(c0, c1), kind=kind)
         d = _lib.Conv3x3Desc()
-        d.algo = _DESC_ALGO[wino]
+        d.algo = _KINDS[kind].algo
         d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cin, c1 - c0, len(srcs)
         for k, s in enumerate(srcs):
             d.src[k] = _nhwc_src(s, f"src{k}")
@@ -1167,14 +1086,14 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
             d.flow, d.fh, d.fw = flow.data_ptr(), flow.shape[1], flow.shape[2]
         if abs_sum is not None:
             d.abs_sum = abs_sum.data_ptr()
-        if wino == 6:
+        if kind == 6:
             d.range_flag = _range_flag(dev).data_ptr()
         with torch.cuda.device(dev), _apply_switch("head"):
             _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
     if _ConvFlops.enabled:
-        for (c0, c1), w_ in zip(slices, fam):
-            _ConvFlops.add("dcn_head_" + _FAMILY[w_], 2.0 * (c1 - c0) * 9 * Cin * H * W * B,
-                           2.0 * (c1 - c0) * 9 * Cin * H * W * B * _EXEC_FACTOR[w_])
+        for (c0, c1), k in zip(slices, fam):
+            f = 2.0 * (c1 - c0) * 9 * Cin * H * W * B
+            _ConvFlops.add("dcn_head_" + _KINDS[k].family, f, f * _KINDS[k].exec_factor)
     return offset, mask
 
 
@@ -1267,7 +1186,7 @@ def refresh_weight_caches(module_or_params=None, all_kinds=False):
         ids = {id(p) for p in params}
     kinds = None
     if not all_kinds and not torch.is_grad_enabled():
-        kinds = {0, 1, 2, 4} if bf16_autocast() else ({0, 1, 2, 6, 7, 8} if _f16x2_auto() else {0, 1, 2, 3})
+        kinds = {0, 1, 2, 4} if bf16_autocast() else ({0, 1, 2, 6} if _f16x2_auto() else {0, 1, 2, 3})
     return _wcache.refresh(ids, kinds) + _dcn_wcache.refresh(ids)
 
 

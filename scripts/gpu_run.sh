@@ -11,29 +11,13 @@ mkdir -p $O
 for stage in "$@"; do
   case $stage in
     smoke)      timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log ;;
-    diag_w16)   (timeout 300 python scripts/diag_wino16.py; timeout 300 python scripts/diag_wino16.py f23) > $O/diag_wino16.log 2>&1 ;;
-    bisect_w16) (for m in 0 1 2 4 3 7; do echo "=== C2M_W16_DBG=$m"; C2M_W16_DBG=$m timeout 120 python scripts/diag_wino16.py 0 2 3 2>&1 | grep -v amdgpu.ids | cut -c1-400; done) > $O/bisect_wino16.log 2>&1 ;;
-    abl_w16)    (for m in ${W16_MASKS:-0 1 2 4 8 16 32 64 3 19 27 59 72 123}; do echo "=== C2M_W16_DBG=$m (1 no re-loads, 2 no items, 4 no weight DMA, 8 no unit-end waits/barriers, 16 one output row of four stored, 32 no MFMAs)"; C2M_W16_DBG=$m timeout 120 python scripts/bench_conv.py --algo ${W16_ALGO:-wino16} --only "64->64 @640" --iters 20 2>&1 | grep "^{'layer"; done) > $O/abl_wino16.log 2>&1 ;;
     abl128)     (for abl in 0 128; do echo "=== C2M_SPLIT_ABL=$abl (128: the first unit-end wait after a tile's epilogue lets its 16 stores stay in flight)"; C2M_SPLIT_ABL=$abl timeout 200 python scripts/bench_conv.py --algo split16 --only "64->64" --iters 20 2>&1 | grep "^{'layer"; done
                  echo "=== conv tests under C2M_SPLIT_ABL=128"; C2M_SPLIT_ABL=128 timeout 600 python -m pytest tests/test_conv_gpu.py -m gpu -q -x -k "split16 and (fp64 or full_size or scales)" 2>&1 | tail -15) > $O/abl128.log 2>&1 ;;
-    pmc_w16)    cd /tmp
-                for a in split16 wino16 wino16_f23; do
-                  timeout 200 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_LDS --kernel-trace -f csv -d $O/pmcw_$a -o c -- python $R/scripts/bench_conv.py --algo $a --only 'body 64->64 @640' --iters 6 > $O/pmcw_$a.log 2>&1
-                  echo "=== --algo $a" >> $O/pmc_wino16.txt
-                  grep "^{'layer" $O/pmcw_$a.log >> $O/pmc_wino16.txt
-                  python $R/scripts/pmc_kernel.py $O/pmcw_$a conv3x3_ >> $O/pmc_wino16.txt 2>&1
-                  timeout 200 rocprofv3 --pmc SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS --kernel-trace -f csv -d $O/pmcx_$a -o c -- python $R/scripts/bench_conv.py --algo $a --only 'body 64->64 @640' --iters 6 > $O/pmcx_$a.log 2>&1
-                  python $R/scripts/pmc_kernel.py $O/pmcx_$a conv3x3_ >> $O/pmc_wino16.txt 2>&1
-                  rm -rf $O/pmcw_$a $O/pmcx_$a
-                done
-                cd $R ;;
     ab_bf)      (for lib in "" $R/build_exp/${AB_LIB:-libc2m_base.so} "" $R/build_exp/${AB_LIB:-libc2m_base.so}; do echo "=== C2M_LIB=$lib"; C2M_LIB=$lib timeout 300 python scripts/bench_conv.py --algo split16 --iters 20 2>&1 | grep "^{'layer"; done) > $O/ab_branch_free.log 2>&1
                 (echo "=== in-tree (branch-free chunk loop)"; timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>&1 | grep "^{" | cut -c1-1600
                  echo "=== C2M_LIB=build_exp/${AB_LIB:-libc2m_base.so}"; C2M_LIB=$R/build_exp/${AB_LIB:-libc2m_base.so} timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-alt 2>&1 | grep "^{" | cut -c1-1600) > $O/ab_branch_free_step.log 2>&1 ;;
     abl_corrf)  (for lib in "" ${CF_LIBS:-cf1 cf2 cf4 cf8 cf16 cf3 cf15} ""; do echo "=== ${lib:-in-tree} (C2M_CORRF_ABL: 1 B operands reused, 2 no ring reads, 4 no tap rounds, 8 no row-sum tail, 16 no MFMAs)"; C2M_LIB=${lib:+$R/build_exp/libc2m_$lib.so} timeout 120 python scripts/abl_corr_filter.py 2>&1 | grep "^{"; done) > $O/abl_corr_filter.log 2>&1 ;;
     abl_c3)     (for lib in "" ${C3_LIBS:-c3a1 c3a2 c3a4 c3a3 c3a7} ""; do echo "=== ${lib:-in-tree} (C2M_C3_ABL: 1 one store of eight, 2 no MFMAs, 4 tile staged once)"; C2M_LIB=${lib:+$R/build_exp/libc2m_$lib.so} timeout 120 python scripts/abl_c3.py 2>&1 | grep "^{"; done) > $O/abl_c3.log 2>&1 ;;
-    test_w16)   timeout 900 python -m pytest tests/test_conv_gpu.py -m gpu -q -rA -k "wino16" 2>&1 | tail -120 > $O/pytest_wino16.log ;;
-    bench_w16)  (for a in split16 wino16 wino16_f23; do echo "== $a"; timeout 200 python scripts/bench_conv.py --algo $a --only "body" --iters 20; done) 2>&1 | grep -v "^\[{" > $O/bench_wino16.log ;;
     test_corr)  timeout 900 python -m pytest tests/test_corr_gpu.py -m gpu -q -rA 2>&1 | tail -80 > $O/pytest_corr.log ;;
     test_conv)  timeout 900 python -m pytest tests/test_conv_gpu.py -m gpu -q -rA 2>&1 | tail -80 > $O/pytest_conv.log ;;
     test_dcn)   timeout 900 python -m pytest tests/test_dcn_gpu.py -m gpu -q -rA 2>&1 | tail -80 > $O/pytest_dcn.log ;;
@@ -215,36 +199,6 @@ PY
                   rm -rf $O/pmcd_$i $O/pmcc_$i
                 done
                 cd $R ;;
-    diag_rb)    timeout 600 python scripts/diag_resblock.py ${RB_ARGS:-check time} > $O/diag_resblock.log 2>&1; echo "rc=$?" >> $O/diag_resblock.log ;;
-    abl_rbk)    (for m in "" ${RBK_MASKS:-8 16 32 40 56 64 120 2} ""; do echo "=== ${m:-in-tree} (C2M_RB_ABL: 1 no stores, 2 no MFMAs, 4 no x loads, 8 no unit-end waits/barriers, 16 no output epilogue, 32 no operand wait before a unit's first tap, 64 no conv1 epilogue)"; C2M_LIB=${m:+$R/build_exp/libc2m_rb$m.so} timeout 200 python scripts/diag_resblock.py time 2>&1 | grep "^{"; done) > $O/abl_resblock_kernel.log 2>&1 ;;
-    abl_rbr)    (for m in 0 ${RBR_MASKS:-1 16 64 80} 0; do echo "=== C2M_RB_ABLR=$m (runtime, no dead-code elimination: 1 no output stores, 16 no output epilogue, 64 no conv1 epilogue)"; C2M_RB_ABLR=$m timeout 200 python scripts/diag_resblock.py time 2>&1 | grep "^{"; done) > $O/abl_resblock_runtime.log 2>&1 ;;
-    pmc_rb)     cd /tmp
-                i=0
-                for set in "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_LDS" \
-                           "SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS" \
-                           "SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD"; do
-                  i=$((i+1))
-                  timeout 300 rocprofv3 --pmc $set --kernel-trace -f csv -d $O/pmcrb_$i -o c -- python $R/scripts/diag_resblock.py time640 > $O/pmcrb_$i.log 2>&1
-                  echo "=== pass $i: $set" >> $O/pmc_resblock.txt
-                  grep "^{" $O/pmcrb_$i.log >> $O/pmc_resblock.txt
-                  python $R/scripts/pmc_kernel.py $O/pmcrb_$i "conv" >> $O/pmc_resblock.txt 2>&1
-                  python - $O/pmcrb_$i <<'PY' >> $O/pmc_resblock.txt 2>&1
-import csv, glob, sys, re
-csv.field_size_limit(1 << 30)
-acc = {}
-for fn in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
-    for r in csv.DictReader(open(fn)):
-        k = r["Kernel_Name"]
-        if "conv" not in k: continue
-        m = re.search(r"(c2m::[A-Za-z0-9_:]+(<[^>(]*>)?)", k); k = m.group(1) if m else k[:60]
-        acc.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6)
-for k, v in acc.items():
-    v.sort(); print("   duration ms under the counters:", k, "median", round(v[len(v)//2], 4), "n", len(v))
-PY
-                  rm -rf $O/pmcrb_$i
-                done
-                cd $R ;;
-    test_exp)   C2M_LIB=$R/build_exp/exp/libc2m_hip.so timeout 1500 python -m pytest tests/test_conv_gpu.py -m gpu -q -rA -k "wino16 or loader_matrix or fused_residual" 2>&1 | tail -90 > $O/pytest_experimental.log ;;
     ab_corrf)   (for lib in "" cf_slow "" cf_slow; do echo "=== ${lib:-in-tree (third-best threshold in front of the top-3 update)} ${lib:+(C2M_CORRF_FAST=0: unconditional update)}"; C2M_LIB=${lib:+$R/build_exp/$lib/libc2m_hip.so} timeout 120 python scripts/abl_corr_filter.py 2>&1 | grep "^{"; C2M_LIB=${lib:+$R/build_exp/$lib/libc2m_hip.so} timeout 300 python bench.py --workload corr --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | grep "^{" | python -c "import sys,json; p=json.loads(sys.stdin.read()); print({'configs1_pairs_per_s': round(p['value'],1), 'ms_per_step': round(p['ms_per_step'],3), 'kernels_ms': p['c2m_kernel_ms_per_step']})"; done) > $O/ab_corr_filter_fast.log 2>&1 ;;
     pmc_conv_ta) cd /tmp
                 i=0

@@ -2,8 +2,6 @@
 
 The operator is floating point; fp32 MFMA is an exact fmaf chain, so the only freedom against a reference convolution is
 the summation order: tolerance 1e-5 * scale against F.conv2d evaluated in float64 (what VERDICT r1 item 7 asks for)."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -291,6 +289,20 @@ def test_conv3x3_rgb64_first_layer_at_full_size(ops, dev):
     assert torch.equal(bo.grouped8, bo.buf.view(B, H + 3, W + 3, 8, 8).permute(0, 3, 1, 2, 4).contiguous())
 
 
+def test_conv3x3_rgb64_rejects_an_oversized_image_before_copying_it(ops, dev):
+    """H * W >= 178 956 971 (12 H W bytes >= 2^31, past the kernel's 32-bit offsets) raises at once: an expanded 13 378^2 view
+    is neither copied (2.1 GB) nor padded to 32 channels first."""
+    import c2m_amd
+    img = torch.rand((1, 3, 1, 1), device=dev).expand(1, 3, 13378, 13378)
+    w = _rand((64, 3, 3, 3), dev, 18)
+    torch.cuda.synchronize(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.max_memory_allocated(dev)
+    with pytest.raises(c2m_amd.C2MError, match="too large"):
+        ops.conv3x3_rgb64(img, w)
+    assert torch.cuda.max_memory_allocated(dev) - before < 1 << 20
+
+
 WINO_CASES = [
     # B, [Cin per source], Cout, H, W, act, n residuals     (W % 32 == 0, Cout % 64 == 0, channels % 16 == 0)
     (2, [64], 64, 12, 64, 1, 0),
@@ -413,132 +425,6 @@ def test_conv3x3_split16_domain(ops, dev):
     e16 = float((ops.conv3x3(xm, w, b, algo="split16").double() - want).abs().max())
     ed = float((ops.conv3x3(xm, w, b, algo="direct").double() - want).abs().max())
     assert e16 < 1e-5 * float(want.abs().max()) and e16 <= 1.5 * ed + 1e-7 * float(want.abs().max()), (e16, ed)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Winograd F(4,3) / F(2,3) ALONG Y on the f16 x 2 pieces (csrc/conv3x3_wino16.hip): "wino16" / "wino16_f23".  Channels-last
-# output, Cout % 64 == 0, any map size.  Opt-in kernels (round 5's go / no-go on VERDICT r4 item 1: DESIGN.md 6.7).  Both are
-# held to 1e-5 * scale against float64.  F(2,3) also meets the split kernel's second criterion (<= 1.5 x the exact-fp32-MFMA
-# "direct" kernel's distance from float64 -- it is in fact closer than the direct f16 x 2 kernel); F(4,3) does NOT (measured
-# 2 - 2.5 x on 64-channel layers, where the fp32 chain itself is short and the transforms' constants dominate): it is held to
-# <= 3 x, and that is one of the two reasons it is not the default.
-# ---------------------------------------------------------------------------------------------------------------------
-WINO16_ALGOS = ("wino16", "wino16_f23")
-
-
-@pytest.fixture
-def experimental(ops):
-    """Round 6: both no-go kernels moved to csrc/experimental/ and out of the product library (`make EXPERIMENTAL=1` builds them)."""
-    if not ops.experimental_built():
-        pytest.skip("libc2m_hip.so built without EXPERIMENTAL=1 (csrc/experimental/ kernels are not in the product library)")
-WINO16_VS_DIRECT = {"wino16": 3.0, "wino16_f23": 1.5}
-WINO16_CASES = [c for c in CASES + WINO_CASES if c[2] % 64 == 0] + [
-    (1, [16], 64, 8, 32, 0, 0),          # one chunk per tile: prologue / first-operand paths only
-    (1, [32], 64, 3, 5, 1, 0),           # map smaller than a tile in both directions
-    (2, [48, 16], 128, 17, 33, 2, 1),    # 16-channel source boundary inside the stream, two cout blocks, ragged tiles
-    (1, [64], 64, 64, 96, 1, 1),         # several tiles per workgroup
-    (1, [32], 64, 390, 392, 1, 0),       # > 256 workgroup slots: persistent workgroups, odd chunk count per stream position
-    (1, [16], 64, 384, 400, 2, 1),       # one-chunk tiles in a long stream (the plane-buffer / ring parities walk through every phase)
-    (1, [48], 64, 50, 61, 0, 2),         # three chunks per tile: odd number of units per tile (ring slot / plane buffer parity per tile)
-]
-
-
-@pytest.mark.parametrize("algo", WINO16_ALGOS)
-@pytest.mark.parametrize("case", WINO16_CASES)
-def test_conv3x3_wino16_matches_fp64_conv2d(experimental, ops, dev, case, algo):
-    B, cins, Cout, H, W, act, nres = case
-    xs = [_cl(_rand((B, c, H, W), dev, 410 + k)) for k, c in enumerate(cins)]
-    w = _rand((Cout, sum(cins), 3, 3), dev, 420, 1.0 / np.sqrt(9 * sum(cins)))
-    b = _rand((Cout,), dev, 421)
-    res = [_cl(_rand((B, Cout, H, W), dev, 430 + k)) for k in range(nres)]
-    kw = dict(act=act, slope=0.1, res1=res[0] if nres > 0 else None, res2=res[1] if nres > 1 else None)
-    got = ops.conv3x3(xs, w, b, algo=algo, **kw)
-    want = _ref(xs, w, b, act, 0.1, res)
-    assert got.shape == want.shape and got.is_contiguous(memory_format=torch.channels_last)
-    scale = max(1.0, float(want.abs().max()))
-    err = float((got.double() - want).abs().max())
-    assert err < 1e-5 * scale, err
-    if algo == {7: "wino16", 8: "wino16_f23"}.get(ops._WINO16) and ops._SPLIT16:   # the automatic choice under a guard / explicit flavour
-        with ops.conv_flavour("f16x2"):
-            auto = ops.conv3x3(xs, w, b, fast=True, **kw)
-        assert torch.equal(auto, got)
-
-
-def test_conv3x3_wino16_is_as_accurate_as_the_fp32_mfma_kernel(experimental, ops, dev):
-    """Same criterion as the direct f16 x 2 kernel's: distance from float64 <= 1.5 x the exact-fp32-MFMA kernel's, in the
-    maximum and in the root-mean-square sense, on K = 9 * 256 products per output (N(0,1) inputs) and on non-negative
-    (post-ReLU-like) inputs, where a Winograd transform's intermediate magnitudes are least favourable."""
-    for kind in ("normal", "relu"):
-        x = _rand((1, 256, 32, 60), dev, 440)
-        if kind == "relu":
-            x = x.clamp_min(0)
-        x = _cl(x)
-        w, b = _rand((256, 256, 3, 3), dev, 441, 1.0 / 48.0), _rand((256,), dev, 442)
-        want = _ref([x], w, b, 0, 0.0, [])
-        outs = {a: ops.conv3x3(x, w, b, algo=a).double() for a in ("direct", "split16") + WINO16_ALGOS}
-        errs = {a: float((o - want).abs().max()) for a, o in outs.items()}
-        rms = {a: float((o - want).pow(2).mean().sqrt()) for a, o in outs.items()}
-        for a in WINO16_ALGOS:
-            assert errs[a] <= WINO16_VS_DIRECT[a] * errs["direct"] + 1e-7, (kind, errs)
-            assert rms[a] <= WINO16_VS_DIRECT[a] * rms["direct"], (kind, rms)
-            assert errs[a] < 1e-5 * max(1.0, float(want.abs().max())), (kind, errs)
-        assert errs["wino16_f23"] <= 1.25 * errs["split16"] + 1e-7 and rms["wino16_f23"] <= 1.1 * rms["split16"], (kind, errs, rms)
-
-
-@pytest.mark.parametrize("algo", WINO16_ALGOS)
-@pytest.mark.parametrize("xs_,ws_", [(1e-3, 1.0), (1e3, 1.0), (1.0, 1e-6), (1.0, 1e5), (3e-3, 2e-4), (250.0, 37.0)])
-def test_conv3x3_wino16_scales(experimental, ops, dev, algo, xs_, ws_):
-    """Away from unit scale (activations 1e-3 ... 1e3, weights of any magnitude) the RELATIVE accuracy of the unit-scale case holds."""
-    x = _cl(_rand((1, 64, 16, 40), dev, 450)) * xs_
-    w, b = _rand((64, 64, 3, 3), dev, 451, 1.0 / 24.0) * ws_, _rand((64,), dev, 452) * (xs_ * ws_)
-    want = _ref([x], w, b, 0, 0.0, [])
-    scale = float(want.abs().max())
-    e16 = float((ops.conv3x3(x, w, b, algo=algo).double() - want).abs().max())
-    ed = float((ops.conv3x3(x, w, b, algo="direct").double() - want).abs().max())
-    assert e16 < 1e-5 * scale and e16 <= WINO16_VS_DIRECT[algo] * ed + 1e-7 * scale, (e16, ed, scale)
-
-
-@pytest.mark.parametrize("algo", WINO16_ALGOS)
-def test_conv3x3_wino16_domain_and_range_flag(experimental, ops, dev, algo):
-    """Domain |x| < 26200 (F(4,3)) / 32760 (F(2,3)): beyond it the kernel raises the range flag (the guarded module forwards then
-    recompute on bf16 x 3) -- below it, mixed magnitudes 1e-6 ... 3e3 keep the tolerance; zero weights give exactly the bias."""
-    x = _cl(_rand((1, 32, 8, 32), dev, 460))
-    w, b = _rand((64, 32, 3, 3), dev, 461, 0.06), _rand((64,), dev, 462)
-    ops.range_flag_set(dev)            # (clear what an earlier test's out-of-domain launch may have reported)
-    assert not ops.range_flag_set(dev)
-    ops.conv3x3(x, w, b, algo=algo)
-    assert not ops.range_flag_set(dev)
-    xb = x.clone()
-    xb[0, 5, 4, 7] = 4.0e4
-    ops.conv3x3(_cl(xb), w, b, algo=algo)
-    assert ops.range_flag_set(dev) and not ops.range_flag_set(dev)     # reported, then cleared
-    z = ops.conv3x3(x, torch.zeros_like(w), b, algo=algo)
-    assert torch.equal(z, b.view(1, -1, 1, 1).expand_as(z))
-    mag = 10.0 ** (_rand((1, 32, 8, 32), dev, 463) * 2.5 - 1.0).clamp(-6.0, 3.5)
-    xm = _cl(x * mag)
-    want = _ref([xm], w, b, 0, 0.0, [])
-    e16 = float((ops.conv3x3(xm, w, b, algo=algo).double() - want).abs().max())
-    ed = float((ops.conv3x3(xm, w, b, algo="direct").double() - want).abs().max())
-    assert e16 < 1e-5 * float(want.abs().max()) and e16 <= WINO16_VS_DIRECT[algo] * ed + 1e-7 * float(want.abs().max()), (e16, ed)
-
-
-@pytest.mark.parametrize("algo", WINO16_ALGOS)
-def test_conv3x3_wino16_full_size_body_conv(experimental, ops, dev, algo):
-    """configs[2]'s own body layer: 64 -> 64 @640^2, B = 16 (chip-filling: 14 080 tiles on 256 workgroups, 55 tiles per stream),
-    ReLU + residual; a sub-block of the LAST sample against float64, the whole tensor against the direct f16 x 2 kernel, and
-    bit-identical results across repeated launches."""
-    x = _cl(_rand((16, 64, 640, 640), dev, 470))
-    w, b = _rand((64, 64, 3, 3), dev, 471, 1.0 / 24.0), _rand((64,), dev, 472)
-    r = _cl(_rand((16, 64, 640, 640), dev, 473))
-    got = ops.conv3x3(x, w, b, act=ops.ACT_RELU, res1=r, algo=algo)
-    ref16 = ops.conv3x3(x, w, b, act=ops.ACT_RELU, res1=r, algo="split16")
-    scale = float(ref16.abs().max())
-    assert float((got - ref16).abs().max()) < 1e-5 * scale
-    for rep in range(2):
-        assert torch.equal(ops.conv3x3(x, w, b, act=ops.ACT_RELU, res1=r, algo=algo), got), rep
-    sub = (slice(15, 16), slice(None), slice(570, 640), slice(560, 640))
-    want = (F.conv2d(x[sub].double(), w.double(), b.double(), padding=1).relu() + r[sub].double())[:, :, 2:, 2:]
-    assert float((got[sub][:, :, 2:, 2:].double() - want).abs().max()) < 1e-5 * float(want.abs().max())
 
 
 @pytest.mark.parametrize("shape", [(2, 45, 70), (1, 64, 96), (3, 8, 32), (1, 200, 130)])
@@ -947,72 +833,3 @@ def test_f16_range_guard_switches_a_module_to_bf16x3(ops, dev):
         assert all(torch.equal(again[k], got[k]) for k in got)
         small = vgg(torch.rand(1, 3, 40, 48, device=dev))         # stays on bf16 x 3 (finite either way)
         assert all(bool(torch.isfinite(v).all()) for v in small.values())
-
-
-def test_loader_matrix_wave_kernel_opt_in(experimental, dev):
-    """csrc/conv3x3_pc.hip ($C2M_CONV_PC=1: the f16 x 2 arithmetic with loader and matrix waves, DESIGN.md 6.10 -- measured
-    slower than the split kernel, kept opt-in): ragged, multi-chunk and chip-filling 64-cout layers against float64 and the
-    fp32-MFMA kernel, bit-identical repeats.  A process of its own: the switch is read once per process."""
-    import subprocess, sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, C2M_CONV_PC="1", C2M_CONV_PC_MINPIX="0")
-    r = subprocess.run([sys.executable, os.path.join(repo, "scripts", "diag_pc.py")], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Round 6: a whole ResidualBlockNoBN (arch_util.py:80-136) in ONE launch (csrc/experimental/conv3x3_resblock.hip; VERDICT r5
-# item 1).  Built, right on hardware, measured 6 - 7 % slower than two launches of the split kernel (DESIGN.md 6.11): a recorded
-# no-go that lives in the experimental library (`make EXPERIMENTAL=1`, $C2M_LIB); these tests skip on the product library.
-# ---------------------------------------------------------------------------------------------------------------------
-RESBLOCK_CASES = [(1, 8, 30, 0), (1, 6, 30, 0), (1, 5, 7, 1), (2, 19, 61, 0), (3, 40, 95, 1), (1, 24, 32, 1), (2, 330, 210, 1), (16, 64, 64, 0)]
-
-
-def _resblock_inputs(dev, B, H, W, seed):
-    x = _cl(_rand((B, 64, H, W), dev, seed))
-    w1 = _rand((64, 64, 3, 3), dev, seed + 1, 1.0 / 24.0)
-    w2 = _rand((64, 64, 3, 3), dev, seed + 2, 1.0 / 24.0)
-    b1, b2 = _rand((64,), dev, seed + 3, 0.1), _rand((64,), dev, seed + 4, 0.1)
-    return x, w1, b1, w2, b2
-
-
-@pytest.mark.parametrize("case", RESBLOCK_CASES)
-def test_fused_residual_block_matches_the_two_launch_path(experimental, ops, dev, case):
-    """out = x + conv2(relu(conv1(x))) (+ res2) in one launch against (a) float64 conv2d -- the split kernel's tolerances: 1e-5 *
-    scale and <= 1.5 x the two-launch path's own distance -- and (b) the two-launch f16 x 2 path itself: the only difference is
-    the identity rebuilt from x's two f16 pieces, <= 2^-22 |x| (asserted at 3 ulp of the output scale).  Ragged maps, maps smaller
-    than a strip / a step, several strips and steps, a priming step inside a strip (B = 16: 256 workgroup ranges)."""
-    B, H, W, with_res2 = case
-    x, w1, b1, w2, b2 = _resblock_inputs(dev, B, H, W, 700 + H)
-    r2 = _cl(_rand((B, 64, H, W), dev, 777)) if with_res2 else None
-    with ops.conv_flavour("f16x2"):
-        got = ops.resblock3x3(x, w1, b1, w2, b2, res2=r2)
-        t = ops.conv3x3(x, w1, b1, act=ops.ACT_RELU, algo="split16")
-        two = ops.conv3x3(t, w2, b2, res1=x, res2=r2, algo="split16")
-    xd = x.double()
-    want = xd + F.conv2d(F.relu(F.conv2d(xd, w1.double(), b1.double(), padding=1)), w2.double(), b2.double(), padding=1)
-    if r2 is not None:
-        want = want + r2.double()
-    scale = max(1.0, float(want.abs().max()))
-    e_f, e_2 = float((got.double() - want).abs().max()), float((two.double() - want).abs().max())
-    assert got.is_contiguous(memory_format=torch.channels_last) and bool(torch.isfinite(got).all())
-    assert e_f < 1e-5 * scale and e_f <= 1.5 * e_2 + 1e-7 * scale, (e_f, e_2)
-    assert float((got - two).abs().max()) <= 3 * 2.0 ** -23 * scale
-
-
-def test_fused_residual_block_full_size_and_domain(experimental, ops, dev):
-    """configs[2]'s own body layer (64 -> 64 @640^2, B = 16: every workgroup range starts inside a strip) against the two-launch
-    path, bit-stable over repeats; an activation beyond the f16 x 2 domain raises the same range flag as the split kernel."""
-    x, w1, b1, w2, b2 = _resblock_inputs(dev, 16, 640, 640, 900)
-    with ops.conv_flavour("f16x2"):
-        a = ops.resblock3x3(x, w1, b1, w2, b2)
-        b = ops.resblock3x3(x, w1, b1, w2, b2)
-        t = ops.conv3x3(x, w1, b1, act=ops.ACT_RELU, algo="split16")
-        two = ops.conv3x3(t, w2, b2, res1=x, algo="split16")
-        assert torch.equal(a, b)
-        assert float((a - two).abs().max()) <= 3 * 2.0 ** -23 * max(1.0, float(two.abs().max()))
-        assert not ops.range_flag_set(dev)
-        xb = x[:1, :, :40, :40].clone(memory_format=torch.channels_last)
-        xb[0, 5, 7, 9] = 7.0e4
-        ops.resblock3x3(xb, w1, b1, w2, b2)
-        assert ops.range_flag_set(dev)
