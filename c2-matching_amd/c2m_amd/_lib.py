@@ -100,6 +100,11 @@ def _declare(L):
     L.c2m_conv3x3_wgrad_f32.argtypes = [_vp, ctypes.POINTER(ConvSrc), _i, _vp, _i, _i, ctypes.c_longlong] + [_i] * 5 + [_vp, _vp, _sz]
     L.c2m_conv3x3_nhwc_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Desc)]
     L.c2m_index_to_flow_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp]
+    L.c2m_contras_loss_workspace_bytes.restype = _sz
+    L.c2m_contras_loss_workspace_bytes.argtypes = [_i] * 6
+    L.c2m_contras_loss_forward_f32.argtypes = [_vp] * 5 + [_i] * 6 + [_vp] * 3 + [_i, _i] + [ctypes.c_float] * 3 + [_vp, _vp, _sz]
+    L.c2m_contras_loss_rows_f32.argtypes = [_vp] + [_i] * 6 + [_vp, _sz] + [_vp] * 5
+    L.c2m_contras_loss_backward_f32.argtypes = [_vp] + [_i] * 6 + [_vp] * 3 + [_i, _i] + [ctypes.c_float] * 3 + [_i] + [_vp] * 4 + [_sz]
 
 
 def lib():

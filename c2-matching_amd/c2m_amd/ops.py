@@ -1360,3 +1360,152 @@ def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, 
         else:
             raise _lib.C2MError(f"vgg_stack_forward: unsupported layer {name}: {type(layer).__name__}")
     return out
+
+
+# ---- contrastive correspondence loss of the extractor training (stages 1-2; csrc/contras_loss.hip) --------------------
+
+CONTRAS_MIN_IDS = 128   # a sample with fewer valid correspondences is skipped (teacher_contras_model.py:155-156)
+
+
+def contras_correspondences(transformed_coordinates, H1, W1, scaling_steps=2, min_ids=CONTRAS_MIN_IDS):
+    """The valid correspondences of a whole batch (the reference's per-sample `warp` + skip test, batched).
+
+    transformed_coordinates [B, >=4*H1 (rows), >=4*W1, >=2]: (x, y) in image pixels; the grid is sampled at [::4, ::4].
+    A position is valid iff 10 < x < 4*W1-10 and 10 < y < 4*H1-10 (strict); pos2 = round((y, x) / 2**scaling_steps)
+    with torch.round (half to even).  Samples with fewer than `min_ids` valid positions are dropped.
+    -> dict: ids [Ntot] int32 (ascending per sample), pos2 [Ntot, 2] int32 (y, x), offsets [B+1] int32, keep [B] bool,
+    counts (host list of rows per sample after the skip), n_valid (host int).  Pure batched torch on the tensor's own
+    device; one small device->host copy for the counts."""
+    tc = transformed_coordinates[:, ::4, ::4, :2]
+    B = tc.shape[0]
+    if tc.shape[1] != H1 or tc.shape[2] != W1:
+        raise ValueError(f"transformed_coordinates[:, ::4, ::4] is {tuple(tc.shape[1:3])}, the feature grid is {(H1, W1)}")
+    x = tc[..., 0].reshape(B, -1)
+    y = tc[..., 1].reshape(B, -1)
+    valid = (x > 10) & (x < 4 * W1 - 10) & (y > 10) & (y < 4 * H1 - 10)
+    keep = valid.sum(1) >= min_ids
+    valid = valid & keep[:, None]
+    counts = valid.sum(1)
+    nz = valid.nonzero()                                  # row-major: sample, then ascending grid index
+    bi, ids = nz[:, 0], nz[:, 1]
+    div = float(2 ** scaling_steps)
+    pos2 = torch.stack([torch.round(y[bi, ids] / div), torch.round(x[bi, ids] / div)], 1).to(torch.int32)
+    offsets = torch.zeros(B + 1, dtype=torch.int32, device=tc.device)
+    offsets[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return {"ids": ids.to(torch.int32).contiguous(), "pos2": pos2.contiguous(), "offsets": offsets, "keep": keep,
+            "counts": [int(c) for c in counts.cpu()], "n_valid": int(keep.sum())}
+
+
+class _ContrasLossFn(torch.autograd.Function):
+    """(f1, f2) -> terms [B, 2] = per-sample (hinge, KL), dists [B, 2] = per-sample (mean pos, mean min(neg1, neg2)).
+    The teacher maps are constants (no gradient); dists is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, f1, f2, tf1, tf2, corr, margin, safe_radius, temperature):
+        B, C, H1, W1 = f1.shape
+        H2, W2 = f2.shape[2], f2.shape[3]
+        teacher = tf1 is not None
+        Ntot, max_n = int(corr["ids"].numel()), max(corr["counts"])
+        L = _lib.lib()
+        nbytes = L.c2m_contras_loss_workspace_bytes(B, C, H1, W1, Ntot, int(teacher))
+        if nbytes == 0:
+            raise _lib.C2MError("c2m_contras_loss_workspace_bytes: invalid shapes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f1.device)
+        out = torch.empty((B, 4), dtype=torch.float32, device=f1.device)
+        with torch.cuda.device(f1.device):
+            _lib.check(L.c2m_contras_loss_forward_f32(
+                _stream(), f1.data_ptr(), f2.data_ptr(), tf1.data_ptr() if teacher else None,
+                tf2.data_ptr() if teacher else None, B, C, H1, W1, H2, W2, corr["ids"].data_ptr(), corr["pos2"].data_ptr(),
+                corr["offsets"].data_ptr(), Ntot, max_n, float(margin), float(safe_radius), float(temperature),
+                out.data_ptr(), ws.data_ptr(), nbytes), "c2m_contras_loss_forward_f32")
+        ctx.meta = (B, C, H1, W1, H2, W2, Ntot, max_n, float(margin), float(safe_radius), float(temperature), teacher, nbytes)
+        ctx.corr = corr
+        corr["_workspace"] = ws          # (contras_loss_rows reads the per-row statistics from it)
+        ctx.save_for_backward(ws)
+        dists = out[:, 1:3].contiguous()
+        ctx.mark_non_differentiable(dists)
+        return out[:, 0::3].contiguous(), dists
+
+    @staticmethod
+    def backward(ctx, g_terms, g_dists):
+        (ws,) = ctx.saved_tensors
+        B, C, H1, W1, H2, W2, Ntot, max_n, margin, radius, tau, teacher, nbytes = ctx.meta
+        corr = ctx.corr
+        g_terms = (g_terms if g_terms is not None else torch.zeros((B, 2), device=ws.device)).float().contiguous()
+        gf1 = torch.empty((B, C, H1, W1), dtype=torch.float32, device=ws.device)
+        gf2 = torch.empty((B, C, H2, W2), dtype=torch.float32, device=ws.device)
+        with torch.cuda.device(ws.device):
+            _lib.check(_lib.lib().c2m_contras_loss_backward_f32(
+                _stream(), B, C, H1, W1, H2, W2, corr["ids"].data_ptr(), corr["pos2"].data_ptr(),
+                corr["offsets"].data_ptr(), Ntot, max_n, margin, radius, tau, int(teacher), g_terms.data_ptr(),
+                gf1.data_ptr(), gf2.data_ptr(), ws.data_ptr(), nbytes), "c2m_contras_loss_backward_f32")
+        return gf1, gf2, None, None, None, None, None, None
+
+
+def contras_loss(f1, f2, transformed_coordinates, margin=1.0, safe_radius=4, scaling_steps=2, teacher=None,
+                 temperature=0.15, distill_weight=15.0):
+    """The extractor-training loss of C2-Matching for a whole batch on the fused gfx950 kernels.
+
+    f1 [B,C,H1,W1], f2 [B,C,H2,W2]: the (student) dense features, float32 on the GPU; gradients flow to both.
+    teacher: None (stage 1, TeacherContrasModel) or a pair (tf1, tf2) of the teacher's features (stage 2,
+    StudentContrasDistillationModel); the teacher is a constant: no gradient reaches it.
+    -> (loss [1], pos_dist, neg_dist) for stage 1, (loss [1], pos_dist, neg_dist, distill_loss) for stage 2 -- the
+    reference's return tuples.  Raises NotImplementedError when every sample has fewer than 128 valid correspondences,
+    as the reference does."""
+    f1, f2 = _dev_f32(f1, "f1"), _dev_f32(f2, "f2")
+    if f1.dim() != 4 or f2.dim() != 4 or f1.shape[:2] != f2.shape[:2] or f1.device != f2.device:
+        raise _lib.C2MError("f1 / f2 must be [B,C,H,W] with equal B, C and device")
+    tf1 = tf2 = None
+    if teacher is not None:
+        tf1, tf2 = (_dev_f32(t.detach(), n) for t, n in zip(teacher, ("teacher f1", "teacher f2")))
+        if tf1.shape != f1.shape or tf2.shape != f2.shape:
+            raise _lib.C2MError("teacher features must have the student's shapes")
+    if not isinstance(transformed_coordinates, torch.Tensor) or not transformed_coordinates.is_cuda:
+        raise _lib.C2MError("transformed_coordinates must be a tensor on the GPU")
+    B, C, H1, W1 = f1.shape
+    corr = contras_correspondences(transformed_coordinates.to(f1.device), H1, W1, scaling_steps)
+    if corr["n_valid"] == 0:
+        raise NotImplementedError("no sample has 128 valid correspondences")
+    H2, W2 = f2.shape[2], f2.shape[3]
+    if corr["pos2"].numel():
+        lim = torch.stack([corr["pos2"].min(0).values, corr["pos2"].max(0).values]).cpu()
+        if int(lim[0].min()) < 0 or int(lim[1, 0]) >= H2 or int(lim[1, 1]) >= W2:
+            raise IndexError(f"pos2 outside the {H2}x{W2} map of f2")
+    terms, dists = _ContrasLossFn.apply(f1, f2, tf1, tf2, corr, margin, safe_radius, temperature)
+    wgt = corr["keep"].to(torch.float32)
+    n = float(corr["n_valid"])
+    if teacher is None:
+        loss = (terms[:, 0] * wgt).sum().view(1) / n
+    else:
+        loss = ((terms[:, 0] + distill_weight * terms[:, 1]) * wgt).sum().view(1) / n
+    pos_dist = (dists[:, 0] * wgt).sum() / n
+    neg_dist = (dists[:, 1] * wgt).sum() / n
+    if teacher is None:
+        return loss, pos_dist, neg_dist
+    return loss, pos_dist, neg_dist, (terms[:, 1] * wgt).sum() / n
+
+
+def contras_loss_rows(f1, f2, transformed_coordinates, margin=1.0, safe_radius=4, scaling_steps=2, teacher=None,
+                      temperature=0.15):
+    """Forward only, for inspection: the per-row statistics of contras_loss for the kept samples, concatenated in
+    sample order -> dict of pos, neg1, neg2 [Ntot] and the arg-mins neg1_idx (grid position in f1) / neg2_idx (row within
+    the sample's valid list) [Ntot] int32, plus the correspondences (ids, pos2, offsets, counts, keep)."""
+    f1, f2 = _dev_f32(f1, "f1"), _dev_f32(f2, "f2")
+    B, C, H1, W1 = f1.shape
+    corr = contras_correspondences(transformed_coordinates.to(f1.device), H1, W1, scaling_steps)
+    if corr["n_valid"] == 0:
+        raise NotImplementedError("no sample has 128 valid correspondences")
+    tf1, tf2 = (None, None) if teacher is None else (_dev_f32(teacher[0], "teacher f1"), _dev_f32(teacher[1], "teacher f2"))
+    with torch.no_grad():
+        _ContrasLossFn.apply(f1, f2, tf1, tf2, corr, margin, safe_radius, temperature)
+    ws = corr.pop("_workspace")
+    N = int(corr["ids"].numel())
+    rows = {k: torch.empty(N, dtype=torch.float32, device=f1.device) for k in ("pos", "neg1", "neg2")}
+    rows.update({k: torch.empty(N, dtype=torch.int32, device=f1.device) for k in ("neg1_idx", "neg2_idx")})
+    with torch.cuda.device(f1.device):
+        _lib.check(_lib.lib().c2m_contras_loss_rows_f32(
+            _stream(), B, C, H1, W1, N, int(teacher is not None), ws.data_ptr(), ws.numel(), rows["pos"].data_ptr(),
+            rows["neg1"].data_ptr(), rows["neg1_idx"].data_ptr(), rows["neg2"].data_ptr(), rows["neg2_idx"].data_ptr()),
+            "c2m_contras_loss_rows_f32")
+    rows.update(corr)
+    return rows

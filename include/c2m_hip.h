@@ -392,6 +392,40 @@ int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H,
  * corres_generation_arch.py:29-46 for the whole batch, without the zero padding (the consumer bounds-checks). */
 int c2m_index_to_flow_f32(c2m_stream_t stream, const int64_t* max_idx, int B, int hq, int wq, float* flow);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Contrastive correspondence loss of the extractor training, stages 1-2 (contras_loss.hip): loss_function of
+ * mmsr/models/teacher_contras_model.py:115-210 and student_contras_distillation_model.py:129-257, all samples at once.
+ *
+ * f1 [B][C][H1][W1], f2 [B][C][H2][W2]: the student's dense features (NCHW fp32).  tf1 / tf2: the teacher's, same
+ * shapes, or both NULL (stage 1: no distillation term).  The valid correspondences are CSR over the batch:
+ * offsets [B+1] (int32, offsets[0] = 0, offsets[B] = Ntot), ids [Ntot] (int32 position y*W1+x in the H1 x W1 grid,
+ * ascending within a sample), pos2 [Ntot][2] (int32 (y, x) in the H2 x W2 grid).  A sample the caller skips has no
+ * rows.  max_n = the largest per-sample row count.  out [B][4] = per-sample means (hinge, pos, min(neg1, neg2), KL);
+ * KL is 0 without a teacher and every entry is 0 for a sample with no rows.
+ * C % 16 == 0 and C <= 512; H1*W1 and H2*W2 <= 2^20 (else C2M_ERR_UNSUPPORTED).  The forward is bitwise reproducible.
+ * The workspace carries what the backward needs: keep it unchanged between the two calls.
+ */
+size_t c2m_contras_loss_workspace_bytes(int B, int C, int H1, int W1, int Ntot, int with_teacher);
+int c2m_contras_loss_forward_f32(c2m_stream_t stream, const float* f1, const float* f2, const float* tf1, const float* tf2,
+                                 int B, int C, int H1, int W1, int H2, int W2, const int* ids, const int* pos2,
+                                 const int* offsets, int Ntot, int max_n, float margin, float safe_radius,
+                                 float temperature, float* out, void* workspace, size_t workspace_bytes);
+/* grad_terms [B][2] (device): dL/d out[b][0] (hinge) and dL/d out[b][3] (KL); the pos / neg columns are statistics and
+ * take no gradient.  grad_f1 / grad_f2 (shapes of f1 / f2) are overwritten.  The scatters into them use fp32 atomics
+ * (neg1 arg-mins may hit any position of f1; rounding may repeat a pos2), so the backward is reproducible only to
+ * rounding.  No gradient reaches the teacher. */
+int c2m_contras_loss_backward_f32(c2m_stream_t stream, int B, int C, int H1, int W1, int H2, int W2, const int* ids,
+                                  const int* pos2, const int* offsets, int Ntot, int max_n, float margin,
+                                  float safe_radius, float temperature, int with_teacher, const float* grad_terms,
+                                  float* grad_f1, float* grad_f2, void* workspace, size_t workspace_bytes);
+
+/* Per-row statistics of the last forward held in `workspace` (inspection of the hard negatives; async device copies):
+ * pos, neg1, neg2 [Ntot] fp32 and the arg-mins neg1_idx [Ntot] (position y*W1+x in the H1 x W1 grid) and
+ * neg2_idx [Ntot] (row within the sample's valid list). */
+int c2m_contras_loss_rows_f32(c2m_stream_t stream, int B, int C, int H1, int W1, int Ntot, int with_teacher,
+                              const void* workspace, size_t workspace_bytes, float* pos, float* neg1, int* neg1_idx,
+                              float* neg2, int* neg2_idx);
+
 #ifdef __cplusplus
 }
 #endif
