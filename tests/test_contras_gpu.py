@@ -146,6 +146,7 @@ def _compare(f1, f2, coords, teacher=None, grads=True, rtol=1e-5, **k):
     d1, d2 = f1.detach().double().requires_grad_(grads), f2.detach().double().requires_grad_(grads)
     tk = {kk: v for kk, v in k.items() if kk in ("margin",)}
     tk.update(radius=k.get("safe_radius", 4), steps=k.get("scaling_steps", 2))
+    tk.update(tau=k.get("temperature", S["temperature"]), wd=k.get("distill_weight", S["distill_weight"]))
     want = restate(d1, d2, coords, teacher=None if teacher is None else (teacher[0].double(), teacher[1].double()), **tk)
     assert len(got) == len(want) == (3 if teacher is None else 4)
     assert got[0].shape == (1,)

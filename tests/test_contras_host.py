@@ -80,7 +80,8 @@ def _numpy_builder(coords, H1, W1, steps):
 
 def _coords_with_edges(B, H1, W1, seed):
     g = torch.Generator().manual_seed(seed)
-    c = (torch.rand(B, 4 * H1, 4 * W1, 2, generator=g) * (4 * max(H1, W1) + 20) - 10)
+    # (x, y) drawn per axis from [-4, 4 * size + 4): some positions fall outside, yet every sample keeps >= 128 rows
+    c = torch.rand(B, 4 * H1, 4 * W1, 2, generator=g) * torch.tensor([4.0 * W1 + 8, 4.0 * H1 + 8]) - 4
     sub = c[:, ::4, ::4]
     # exact boundary values (strict comparisons) and exact halves after the /4 (half to even)
     edge = torch.tensor([10.0, 4 * W1 - 10.0, 10.0001, 4 * W1 - 10.0001, 18.0, 22.0, 26.0, 30.0, 14.0, 34.0])
@@ -92,19 +93,51 @@ def _coords_with_edges(B, H1, W1, seed):
     return c
 
 
-@pytest.mark.parametrize("H1,W1,steps", [(20, 20, 2), (16, 24, 2), (24, 16, 3)])
+@pytest.mark.parametrize("H1,W1,steps", [(20, 20, 2), (16, 24, 2), (24, 16, 3), (33, 21, 3), (24, 36, 2)])
 def test_host_builder_matches_numpy_restatement(H1, W1, steps):
     import c2m_amd
-    c = _coords_with_edges(4, H1, W1, 11 + H1 + steps)
-    c[2, ::4, ::4, 0] = 5.0                      # sample 2: nothing valid -> skipped
-    r = c2m_amd.ops.contras_correspondences(c, H1, W1, steps)
-    ids, pos2, counts = _numpy_builder(c.numpy(), H1, W1, steps)
-    assert r["counts"] == counts and counts[2] == 0
-    assert r["n_valid"] == sum(1 for n in counts if n > 0)
-    assert r["offsets"].tolist() == np.concatenate([[0], np.cumsum(counts)]).tolist()
-    assert np.array_equal(r["ids"].numpy(), ids) and r["ids"].dtype == torch.int32
-    assert np.array_equal(r["pos2"].numpy(), pos2) and r["pos2"].dtype == torch.int32
-    assert r["keep"].tolist() == [n > 0 for n in counts]
+    base = _coords_with_edges(4, H1, W1, 11 + H1 + steps)
+    # skipped samples: the middle one (2), the first, the first and a middle one, two neighbours, the last, none
+    for skipped in ((2,), (0,), (0, 2), (1, 2), (3,), ()):
+        c = base.clone()
+        for b in skipped:
+            c[b, ::4, ::4, 0] = 5.0              # nothing valid -> skipped
+        r = c2m_amd.ops.contras_correspondences(c, H1, W1, steps)
+        ids, pos2, counts = _numpy_builder(c.numpy(), H1, W1, steps)
+        assert r["counts"] == counts and [b for b in range(4) if counts[b] == 0] == list(skipped)   # the others are live
+        assert r["n_valid"] == sum(1 for n in counts if n > 0) == 4 - len(skipped)
+        off = r["offsets"].tolist()
+        assert off == np.concatenate([[0], np.cumsum(counts)]).tolist() and r["offsets"].dtype == torch.int32
+        assert all(off[b] == off[b + 1] for b in skipped) and all(off[b] <= off[b + 1] for b in range(4))
+        assert np.array_equal(r["ids"].numpy(), ids) and r["ids"].dtype == torch.int32
+        assert np.array_equal(r["pos2"].numpy(), pos2) and r["pos2"].dtype == torch.int32
+        assert r["keep"].tolist() == [n > 0 for n in counts]
+        for b in range(4):                       # ascending grid indices within every sample
+            assert bool((r["ids"][off[b]:off[b + 1]].diff() > 0).all())
+
+
+def test_unsupported_channel_counts_write_nothing():
+    """C = 24 (not a multiple of 16) and C = 528 (above 512) answer C2M_ERR_UNSUPPORTED (2) from the forward and the
+    backward before any device work: the buffers handed in (host memory here) keep their contents."""
+    import c2m_amd
+    L = c2m_amd._lib.lib()
+    n = 200
+    for C in (24, 528):
+        f = np.ones(C * 400, np.float32)
+        ids, pos2 = np.arange(n, dtype=np.int32), np.zeros(2 * n, np.int32)
+        off = np.array([0, n], np.int32)
+        out, gf = np.full(4, 7.0, np.float32), np.full(C * 400, 5.0, np.float32)
+        ws, g = np.full(1 << 16, 3, np.uint8), np.ones(2, np.float32)
+        p = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+        assert L.c2m_contras_loss_forward_f32(None, p(f), p(f), None, None, 1, C, 20, 20, 20, 20, p(ids), p(pos2), p(off), n, n,
+                                              1.0, 4.0, 0.15, p(out), p(ws), 1 << 30) == 2
+        assert L.c2m_contras_loss_backward_f32(None, 1, C, 20, 20, 20, 20, p(ids), p(pos2), p(off), n, n, 1.0, 4.0, 0.15, 0,
+                                               p(g), p(gf), p(gf), p(ws), 1 << 30) == 2
+        assert (out == 7.0).all() and (gf == 5.0).all() and (ws == 3).all() and (f == 1.0).all()
+        # the neighbours on the admitted side get past the channel check (and stop at the workspace size: 3)
+    for C in (16, 512):
+        assert L.c2m_contras_loss_forward_f32(None, *[ctypes.c_void_p(8)] * 4, 1, C, 20, 20, 20, 20, *[ctypes.c_void_p(8)] * 3,
+                                              n, n, 1.0, 4.0, 0.15, ctypes.c_void_p(8), ctypes.c_void_p(8), 16) == 3
 
 
 def test_host_builder_rounds_half_to_even_and_margins_are_strict():
