@@ -543,7 +543,16 @@ def _nhwc_src(t, name, bf16_ok=False):
     sb, sc, sh, sw = t.stride()
     if sc != 1:
         raise _lib.C2MError(f"{name} must be channels-last (stride 1 along C); got strides {t.stride()}")
-    return _lib.ConvSrc(t.data_ptr(), t.shape[1], sw, sh, sb)
+    # torch leaves the stride of a size-1 dimension arbitrary (a [B,C,1,1] tensor is channels-last with strides (C,1,1,1)) and
+    # no index ever multiplies it: where such a stride would fail the kernels' 16-byte pitch checks, describe the dense layout
+    B, C, H, W = t.shape
+    if W == 1 and sw % 8 != 0:
+        sw = (C + 7) // 8 * 8
+    if H == 1 and sh % 8 != 0:
+        sh = W * sw
+    if B == 1 and sb % 8 != 0:
+        sb = H * sh
+    return _lib.ConvSrc(t.data_ptr(), C, sw, sh, sb)
 
 
 def empty_nhwc(B, C, H, W, device, dtype=torch.float32):
