@@ -903,7 +903,6 @@ __global__ void __launch_bounds__(256) conv3x3_relayout_wino4_kernel(const float
                  : "memory");                                                                                         \
     break;
 
-template <int ABL>   // 0; > 0: timing-only ablations (wrong results): 1 no barriers / DMA waits, 2 no epilogue, 3 no halo DMA
 __global__ void __launch_bounds__(256, 1) conv3x3_wino4_kernel(Params p) {
   constexpr int KC = wino4::KC, TWX = wino4::TWX, THY = wino4::THY, HWc = wino4::HWc, HHr = wino4::HHr;
   constexpr int NIN_REAL = wino4::NIN_REAL, NIN_W = wino4::NIN_W, IN_BYTES = wino4::IN_BYTES, WUNIT = wino4::WUNIT;
@@ -1158,13 +1157,11 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino4_kernel(Params p) {
           __builtin_amdgcn_sched_barrier(0);
         }
         if (gu + 1 < T) {
-          if constexpr (ABL != 1) {
-            if (uc == 0 && gc >= 1 && more_in) wait_vmcnt<NIN_W>();
-            else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-          }
+          if (uc == 0 && gc >= 1 && more_in) wait_vmcnt<NIN_W>();
+          else wait_vmcnt<0>();
+          __builtin_amdgcn_s_barrier();
           if (gu + 3 < T) issue_w(uc % NRING);
-          if (ABL != 3 && uc == UPC - 1 && gc + 2 < G) issue_in(gc + 2);
+          if (uc == UPC - 1 && gc + 2 < G) issue_in(gc + 2);
         }
       }
     }
@@ -1178,7 +1175,6 @@ __global__ void __launch_bounds__(256, 1) conv3x3_wino4_kernel(Params p) {
     const float* r1 = p.res1 ? p.res1 + opix + co_lane : nullptr;
     const float* r2 = p.res2 ? p.res2 + opix + co_lane : nullptr;
     float* ob = p.out + opix + co_lane;
-    if (ABL == 2 && it > 0) { init_m(); continue; }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1256,11 +1252,6 @@ struct Params {
 };
 }  // namespace c3
 
-// C2M_C3_ABL (compile-time, measurement builds only; scripts/abl_c3.py): 1 one store of eight, 2 no MFMAs, 4 the image tile is
-// fetched and staged once per workgroup
-#ifndef C2M_C3_ABL
-#define C2M_C3_ABL 0
-#endif
 template <int ACT, bool OUT2>
 __global__ void __launch_bounds__(256, 2) conv3x3_c3_kernel(c3::Params p) {
   using namespace c3;
@@ -1371,9 +1362,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c3_kernel(c3::Params p) {
   }
   for (int it = 0; t < ntile; t += gridDim.x, ++it) {
     __syncthreads();   // tile `it` staged; everybody has left tile it - 1
-    if (!(C2M_C3_ABL & 4)) fetch(min(t + (int)gridDim.x, ntile - 1));
+    fetch(min(t + (int)gridDim.x, ntile - 1));
     const int tx = t % p.tiles_x, ty = (t / p.tiles_x) % p.tiles_y, b = t / (p.tiles_x * p.tiles_y);
-    const unsigned tb = lds0 + ((C2M_C3_ABL & 4) ? 0 : it & 1) * (NEL * 4);
+    const unsigned tb = lds0 + (it & 1) * (NEL * 4);
     // store descriptors start at this tile's first pixel row (and, for the twin, at each 8-channel plane): the 32-bit offsets
     // then span eight rows whatever the image size
     float* const obase = p.out + (size_t)b * p.out_img_pitch + (size_t)(ty * CTH) * p.out_row_pitch;
@@ -1399,10 +1390,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c3_kernel(c3::Params p) {
 #pragma unroll
       for (int k = 0; k < 14; ++k)
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          if (C2M_C3_ABL & 2) acc[mt][k] += wreg[k][mt] * bv[k];
-          else acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[k][mt], bv[k], acc[mt], 0, 0, 0);
-        }
+        for (int mt = 0; mt < 2; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wreg[k][mt], bv[k], acc[mt], 0, 0, 0);
       const int y = ty * CTH + row, x = tx * CTW + col + j;
       {
         const unsigned bad = (unsigned)(y >= p.H) | (unsigned)(x >= p.W);
@@ -1419,7 +1407,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c3_kernel(c3::Params p) {
               if (ACT == 1) v[e] = fmaxf(v[e], 0.0f);
               else if (ACT == 2) v[e] = fmaxf(v[e], v[e] * p.slope);
             }
-            if ((C2M_C3_ABL & 1) && (mt + qd != 0) && v[0] != 12345.678f) continue;
             // (the channel offset goes into the instruction's IMMEDIATE offset, the plane offset into the vector offset: a 128-bit
             // buffer store with an SGPR soffset whose data registers a VALU overwrites within two issue slots stores garbage in
             // lanes 12..15 / 28..31 of each half on gfx950 -- hipcc pads only the immediate-soffset form of that hazard)
@@ -1432,7 +1419,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_c3_kernel(c3::Params p) {
           }
       }
     }
-    if (!(C2M_C3_ABL & 4)) stage_to(tile[(it + 1) & 1]);
+    stage_to(tile[(it + 1) & 1]);
   }
 }
 
@@ -1688,24 +1675,8 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   if (wino4) {
     static unsigned long long done_w4 = 0;
     const size_t lds4 = 2 * conv::wino4::IN_BYTES + conv::wino4::NRING * conv::wino4::WUNIT + 1024 + 256;
-    // C2M_CONV_ABL = 1..3: timing-only ablations of the F(4,3) kernel (see its template parameter); results are WRONG
-    static const int abl = [] {
-      const char* e = getenv("C2M_CONV_ABL");
-      const int v = e ? atoi(e) : 0;
-      if (v > 0) fprintf(stderr, "c2m: C2M_CONV_ABL=%d -- conv3x3 F(4,3) runs a timing-only ablation, its results are wrong\n", v);
-      return v;
-    }();
-    static unsigned long long done_abl[4] = {};
-    auto go4 = [&](auto kern, unsigned long long& dn) {
-      if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds4, dn)) == C2M_OK)
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds4, st, p);
-    };
-    switch (abl) {
-      case 1: go4(&conv::conv3x3_wino4_kernel<1>, done_abl[1]); break;
-      case 2: go4(&conv::conv3x3_wino4_kernel<2>, done_abl[2]); break;
-      case 3: go4(&conv::conv3x3_wino4_kernel<3>, done_abl[3]); break;
-      default: go4(&conv::conv3x3_wino4_kernel<0>, done_w4); break;
-    }
+    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv::conv3x3_wino4_kernel), lds4, done_w4)) == C2M_OK)
+      hipLaunchKernelGGL(conv::conv3x3_wino4_kernel, grid, dim3(256), lds4, st, p);
   } else if (wino) {
     static unsigned long long done_w[2][2] = {};
     const size_t ldsw = 2 * conv::wino::IN_BYTES + conv::wino::NRING * conv::wino::WUNIT + 1024 + 256;

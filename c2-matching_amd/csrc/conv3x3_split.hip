@@ -60,10 +60,9 @@ constexpr int KC = 16;                          // input channels per chunk = K 
 constexpr int TWX = 32, THY = 8;                // pixel tile of a workgroup
 constexpr int HWc = TWX + 2, HHr = THY + 2;     // halo tile 34 x 10
 constexpr int NPIX = HWc * HHr;                 // 340
-constexpr int NRAW_W = (NPIX * 4 + 255) / 256;  // 6 DMA instructions per wave: 64 pieces of 16 B = (pixel, 4 fp32 channels)
-constexpr int NRAW = 4 * NRAW_W;                // 24 slots (22 carry pixels; the rest read zeros) -- every wave runs the
-                                                // same branch-free sequence of DMAs and split rounds
-constexpr int RAW_BYTES = NRAW * 1024;
+constexpr int NRAW_W = (NPIX * 4 + 255) / 256;  // 6 loads per wave: 64 pieces of 16 B = (pixel, 4 fp32 channels).  4 waves x 6 = 24
+                                                // slots (22 carry pixels; the rest read zeros) -- every wave runs the same
+                                                // branch-free sequence of loads and split rounds
 constexpr int HALFB = NPIX * 16;                // one (plane, k half) slab: 340 pixels x 16 B (the slots beyond are never stored).
                                                 // ds_write_b64 is serviced in groups of 16 consecutive lanes over 32 banks ((a/4) mod 32,
                                                 // MI355X_MICROARCH.md): a group of the split's stores covers 4 pixels x 16 B in each k-half
@@ -271,16 +270,19 @@ __device__ __forceinline__ void lds_write64(unsigned addr, const u32x2 v) {
   asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(IMM) : "memory");
 }
 
-// ABL > 0: timing-only ablations (WRONG results; $C2M_SPLIT_ABL), a bit mask: 1 no weight DMA after the prologue, 2 no halo
-// DMA, 4 no split of the raw tile (only together with 2: loads into dead registers are unsafe), 8 no unit-end waits /
-// barriers, 16 no MFMAs, 32 no operand reads
-// IO16 (bf16 flavour, channels-last mode, one source): the source tensor holds bf16 -- 16 channels of a pixel are two 16-byte
+// conv3x3_split_kernel<FL, MT, MODE, IO16>: a persistent workgroup takes Params::tpw consecutive tiles of 32 x 8 pixels x 32*MT output
+// channels through prologue, chunk loop and epilogue (mapping: top of the file).
+//   FL    arithmetic (struct Flavour): 3 bf16 x 3, 2 f16 x 2, 1 bf16
+//   MT    32-channel output tiles per workgroup: 1 for Cout <= 32, else 2
+//   MODE  epilogue (Params::out_mode): 0 channels-last (+ residuals), 1 PixelShuffle(2), 2 planar NCHW, 3 DCN offset/mask head with
+//         dword stores, 5 the same head with quad-transposed 16-byte stores (W % 4 == 0), 4 ReLU + MaxPool2d(2,2)
+//   IO16  (bf16 flavour, channels-last mode, one source): the source tensor holds bf16 -- 16 channels of a pixel are two 16-byte
 // pieces that ARE plane entries, so the halo tile goes HBM -> LDS by LDS-DMA (no registers, no split rounds, 3 pieces per wave
 // and chunk instead of 6 register loads; zero fill outside the image by the buffer's range check), two chunks ahead into a
 // ring of THREE plane buffers.  Output / residual element types follow Params::io_flags (any FL = 1 launch).
-template <int FL, int MT, int MODE, int ABL = 0, bool IO16 = false>
+template <int FL, int MT, int MODE, bool IO16 = false>
 __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
-  static_assert(!IO16 || (FL == 1 && MODE == 0 && (ABL & 4) == 0), "bf16 sources: the bf16 flavour's channels-last mode");
+  static_assert(!IO16 || (FL == 1 && MODE == 0), "bf16 sources: the bf16 flavour's channels-last mode");
   constexpr int NT = 2;
   constexpr int MW = 32 * MT;
   using PR = Flavour<FL>;
@@ -290,17 +292,10 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
   // PIPE: two plane buffers -- the split of chunk c+1 is interleaved with the MFMAs of chunk c (no phase (A), no barrier for
   // it).  The bf16 x 3 flavour keeps one buffer and phase (A): two of its workgroups would not fit a CU otherwise.
   constexpr bool PIPE = FL != 3;
-  // BF (round 5): the chunk loop of the pipelined fp32-tensor flavours runs WITHOUT uniform branches around its asynchronous
-  // issues: past the end of the workgroup's stream the weight pieces land in the dummy page, the halo loads go through a
-  // descriptor of zero records (no memory traffic, zeros into dead registers) and the split rounds write a plane buffer nobody
-  // reads -- so every unit issues exactly the same vector-memory instructions and its end waits with ONE constant count.
-  // (38 branches per 108 MFMAs before.)
-#ifndef C2M_SPLIT_BF
-#define C2M_SPLIT_BF 1
-#endif
-  constexpr bool BFA = ABL == 0 && C2M_SPLIT_BF != 0;   // any flavour: weight pieces / unit-end waits without branches
-  constexpr bool BF = BFA && !IO16;                     // register-loaded halo tiles (fp32 sources)
-  constexpr bool BF16S = BFA && IO16;                   // LDS-DMA halo tiles (bf16 sources)
+  // The chunk loop runs WITHOUT uniform branches around its asynchronous issues: past the end of the workgroup's stream the
+  // weight pieces land in the dummy page, the halo loads go through a descriptor of zero records (no memory traffic, zeros
+  // into dead registers; bf16 sources: into a plane buffer nobody reads) and the split rounds write a plane buffer nobody reads
+  // -- so every unit issues exactly the same vector-memory instructions and its end waits with ONE constant count.
   constexpr int NPB = IO16 ? 3 : (PIPE ? 2 : 1);
   constexpr int NRING = PIPE ? 3 : 2;           // weight ring slots; unit u's weights are issued NRING-1 units ahead
   constexpr int WTAP = NPW * MT * 1024;         // one tap's weight image: [image][mt][half][32 rows][16 B]
@@ -426,14 +421,14 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
     in_soff = (in_first ? c0 : c0 - p.src[0].C) * 4;
   };
   // IO16: piece `sl` of the chunk issue_in_begin() has just set up -> plane buffer at byte offset `plane_off`
-  __amdgpu_buffer_rsrc_t in_rs16_cur = in_rs16;   // BF16S: in_rs16, or a descriptor of zero records past the stream's end
+  __amdgpu_buffer_rsrc_t in_rs16_cur = in_rs16;   // in_rs16, or a descriptor of zero records past the stream's end
   const __amdgpu_buffer_rsrc_t null_rs16 = make_rsrc(p.src[0].ptr, 0u);
   auto issue_in_dma = [&](int sl, unsigned plane_off) __attribute__((always_inline)) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(BF16S ? in_rs16_cur : in_rs16, (__attribute__((address_space(3))) void*)(pl_base + plane_off + (unsigned)(wv + 4 * sl) * 1024u), 16,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(in_rs16_cur, (__attribute__((address_space(3))) void*)(pl_base + plane_off + (unsigned)(wv + 4 * sl) * 1024u), 16,
                                              dvoff[sl], in_soff, 0, 0);
   };
   f32x4 rawr[NRAW_W];
-  i32x4 rs_cur = {0, 0, 0, 0x00020000};   // BF: descriptor of the chunk being fetched (set_chunk_rsrc)
+  i32x4 rs_cur = {0, 0, 0, 0x00020000};   // descriptor of the chunk being fetched (set_chunk_rsrc)
   auto set_chunk_rsrc = [&](bool live) __attribute__((always_inline)) {
     const i32x4 r = in_first ? rs0 : rs1;
     rs_cur[0] = r[0];
@@ -443,12 +438,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
   };
   auto issue_in_piece = [&](auto slc) __attribute__((always_inline)) {
     constexpr int sl = decltype(slc)::value;
-    if constexpr (BF) {
-      buf_load128f(rawr[sl], ivoff[sl], rs_cur, in_soff);
-    } else {
-      if (in_first) buf_load128f(rawr[sl], ivoff[sl], rs0, in_soff);
-      else buf_load128f(rawr[sl], ivoff[sl], rs1, in_soff);
-    }
+    buf_load128f(rawr[sl], ivoff[sl], rs_cur, in_soff);
   };
 
   // ---- split of the wave's own raw pieces into the bf16 planes.  Round r: piece 64 (wv + 4r) + l = (pixel 16 (wv + 4r) +
@@ -497,9 +487,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
   };
   auto load_b = [&](auto setc, auto dyc, auto dxc, auto kc, unsigned bcur) __attribute__((always_inline)) {   // bcur = bbase + plane buffer
     constexpr int SET = decltype(setc)::value, DY = decltype(dyc)::value, DX = decltype(dxc)::value, K = decltype(kc)::value;
-    // (ablation 2048, timing only: the B operand of pixel row nt = 0 at kernel row dy >= 1 is the one row nt = 1 read at dy - 1 -- skip
-    // the re-read, 12 of a chunk's 36 B reads: what holding a unit's four pixel rows in registers would save)
-    if constexpr ((ABL & 2048) != 0 && (K % NT) == 0 && DY >= 1) return;
     lds_read128<(K / NT) * 2 * HALFB + ((K % NT + DY) * HWc + DX) * 16>(Bq[SET][K / NT][K % NT], bcur);
   };
 
@@ -519,24 +506,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
 
-  // ABL & 1024 (-DC2M_SPLIT_TRACE builds only; scripts/trace_split.py): a timeline of two tiles per wave -- s_memtime just before and just
-  // after every unit-end barrier and after the epilogue, kept in the 64 lanes of ONE register and stored once, at the kernel's
-  // end, to Params::mask_out [workgroup][wave][64]; lanes 62 / 63 carry XCC_ID / HW_ID (which CU the workgroup ran on).  Every stamp sits
-  // where lgkmcnt is already zero, so the s_waitcnt it needs costs the timestamp's own latency only.
-  unsigned trace_v = 0u;
-  int trace_it = -1;   // tile slot (0 / 1) being traced, or -1
-  auto stamp = [&](int ev) __attribute__((always_inline)) {
-    if constexpr ((ABL & 1024) != 0) {
-      if (trace_it >= 0) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        const unsigned tl = (unsigned)t;
-        const int ln = trace_it * 26 + ev;
-        trace_v = l == ln ? tl : trace_v;   // (v_writelane_b32 with two SGPR operands violates gfx9's constant-bus limit)
-      }
-    }
-  };
-
   // ------------------------------------------------------------------------------------------------------------------
   // prologue: the raw pieces of chunk 0 and the weights of unit 0
   // ------------------------------------------------------------------------------------------------------------------
@@ -546,7 +515,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
 #pragma unroll
     for (int sl = 0; sl < 3; ++sl) issue_in_dma(sl, 0u);
   } else {
-    if constexpr (BF) set_chunk_rsrc(true);
+    set_chunk_rsrc(true);
     static_for<0, NRAW_W>([&](auto rr) __attribute__((always_inline)) { issue_in_piece(rr); });
   }
 #pragma unroll
@@ -572,9 +541,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
   }
   wait_vmcnt<0>();
   if constexpr (PIPE && !IO16) {   // chunk 0 -> plane buffer 0; the registers re-load with chunk 1
-    const bool more1 = !(ABL & 2) && G > 1;
+    const bool more1 = G > 1;
     if (more1) issue_in_begin();
-    if constexpr (BF) set_chunk_rsrc(more1);
+    set_chunk_rsrc(more1);
     static_for<0, NRAW_W>([&](auto rr) __attribute__((always_inline)) {
       constexpr int R = decltype(rr)::value;
       conv_split(rawr[R]);
@@ -595,35 +564,28 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
   // weights, one per group.  Unit end: own LDS ops / weight DMAs done (the two raw loads issued after them may still fly),
   // barrier (publishes W(u+1) and the other plane buffer, frees this one / the ring slot).
   constexpr int NG = PR::N;
-#ifndef C2M_LPGD
-#define C2M_LPGD 2
-#endif
-  constexpr int LPGD = C2M_LPGD;
+  constexpr int LPGD = 2;   // f16 x 2: a tap's operand reads spread over its first two groups
   constexpr int LPG = NG >= 4 ? (NLA + NLB + NG - 3) / (NG - 2) : (NG == 3 ? (NLA + NLB + LPGD - 1) / LPGD : NLA + NLB);   // operand reads per group
   static_assert(NRAW_W == 6, "two split rounds per unit");
   unsigned slot_cur = 0u;   // ring slot (byte offset) of the current unit
   for (int it = 0, gc = 0; it < ntl; ++it) {
-    if constexpr ((ABL & 1024) != 0) trace_it = (it >= p.co_off && it < p.co_off + 2 && p.nchunks <= 4) ? it - p.co_off : -1;
     for (int c = 0; c < p.nchunks; ++c, ++gc) {
       // PIPE: the registers hold chunk gc+1 (if any); they re-load with chunk gc+2.  Else: they hold chunk gc, re-load with gc+1
-      const bool has_next = PIPE ? gc + 1 < G : true;
-      const bool more_in = !(ABL & 2) && gc + (PIPE ? 2 : 1) < G;
+      const bool more_in = gc + (PIPE ? 2 : 1) < G;
       const unsigned pb = IO16 ? (unsigned)(gc % 3) * PLB : PIPE ? (unsigned)(gc & 1) * PLB : 0u;
       const unsigned pb_in = (unsigned)((gc + 2) % 3) * PLB;   // IO16: where chunk gc+2 lands
       const unsigned bcur = bbase + pb, cnext = PIPE ? cdst + (PLB - pb) : cdst;
       if (more_in) issue_in_begin();
-      if constexpr (BF) set_chunk_rsrc(more_in);
-      if constexpr (BF16S) in_rs16_cur = more_in ? in_rs16 : null_rs16;
+      if constexpr (IO16) in_rs16_cur = more_in ? in_rs16 : null_rs16;
+      else set_chunk_rsrc(more_in);
       if constexpr (!PIPE) {
         // ---- (A) split
-        if constexpr (!(ABL & 4)) {
-          static_for<0, NRAW_W>([&](auto rr) __attribute__((always_inline)) {
-            constexpr int R = decltype(rr)::value;
-            conv_split(rawr[R]);
-            conv_store(rr, cdst);
-            if (BF || more_in) issue_in_piece(rr);    // same slot of the next chunk
-          });
-        }
+        static_for<0, NRAW_W>([&](auto rr) __attribute__((always_inline)) {
+          constexpr int R = decltype(rr)::value;
+          conv_split(rawr[R]);
+          conv_store(rr, cdst);
+          issue_in_piece(rr);    // same slot of the next chunk
+        });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
       }
@@ -631,10 +593,13 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
       static_for<0, 3>([&](auto dyc) __attribute__((always_inline)) {
         constexpr int dy = decltype(dyc)::value;
         const int u = 3 * gc + dy;
+        // (names `c` so that this closure captures it, as it did while the unit ends carried timestamps: without that field hipcc
+        // assigns the scalar registers of the f16 x 2, 64-cout kernels' epilogues differently -- DESIGN.md 6.15.  No code.)
+        (void)c;
         // weights of unit u + NRING - 1 -> the slot unit u - 1 has just left
         const unsigned slot_nxt = slot_cur == 0u ? (unsigned)((NRING - 1) * WUNIT) : slot_cur - (unsigned)WUNIT;
         const unsigned aslot = abase + slot_cur;
-        const bool do_w = !(ABL & 1) && u + NRING - 1 < 3 * G;
+        const bool do_w = u + NRING - 1 < 3 * G;
         // operands of the unit's first tap: A now (its weights were published by the barrier just passed); B too at dy == 0
         static_for<0, NLA>([&](auto kc) __attribute__((always_inline)) {
           load_a(std::integral_constant<int, (dy & 1)>(), std::integral_constant<int, 0>(), kc, aslot);
@@ -651,30 +616,21 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
           __builtin_amdgcn_sched_barrier(0);
           static_for<0, NG>([&](auto gcnt) __attribute__((always_inline)) {
             constexpr int g = decltype(gcnt)::value;
-            if constexpr (!(ABL & 32)) {
-              // next tap's operands: (dy, dx+1): A and B; after the unit's last tap: only B of (dy+1, 0)
-              static_for<g * LPG, (g + 1) * LPG < NLA + NLB ? (g + 1) * LPG : NLA + NLB>([&](auto kc) __attribute__((always_inline)) {
-                constexpr int K = decltype(kc)::value;
-                if constexpr (dx < 2) {
-                  if constexpr (K < NLA) load_a(std::integral_constant<int, nset>(), std::integral_constant<int, dx + 1>(), kc, aslot);
-                  else load_b(std::integral_constant<int, nset>(), dyc, std::integral_constant<int, dx + 1>(), std::integral_constant<int, K - NLA>(), bcur);
-                } else if constexpr (dy < 2) {
-                  if constexpr (K >= NLA)
-                    load_b(std::integral_constant<int, nset>(), std::integral_constant<int, dy + 1>(), std::integral_constant<int, 0>(),
-                           std::integral_constant<int, K - NLA>(), bcur);
-                }
-              });
-            }
-            if constexpr (dx == 0) {
-              if constexpr (BFA) {
-#pragma unroll
-                for (int i = g; i < NW_W; i += NG) issue_w_piece(slot_nxt, i, do_w);
-              } else {
-                if (do_w) {
-#pragma unroll
-                  for (int i = g; i < NW_W; i += NG) issue_w_piece(slot_nxt, i);
-                }
+            // next tap's operands: (dy, dx+1): A and B; after the unit's last tap: only B of (dy+1, 0)
+            static_for<g * LPG, (g + 1) * LPG < NLA + NLB ? (g + 1) * LPG : NLA + NLB>([&](auto kc) __attribute__((always_inline)) {
+              constexpr int K = decltype(kc)::value;
+              if constexpr (dx < 2) {
+                if constexpr (K < NLA) load_a(std::integral_constant<int, nset>(), std::integral_constant<int, dx + 1>(), kc, aslot);
+                else load_b(std::integral_constant<int, nset>(), dyc, std::integral_constant<int, dx + 1>(), std::integral_constant<int, K - NLA>(), bcur);
+              } else if constexpr (dy < 2) {
+                if constexpr (K >= NLA)
+                  load_b(std::integral_constant<int, nset>(), std::integral_constant<int, dy + 1>(), std::integral_constant<int, 0>(),
+                         std::integral_constant<int, K - NLA>(), bcur);
               }
+            });
+            if constexpr (dx == 0) {
+#pragma unroll
+              for (int i = g; i < NW_W; i += NG) issue_w_piece(slot_nxt, i, do_w);
             }
             if constexpr (FL == 2 && g == 0) {   // wB = 2^-11 wA of this tap (used by group 1)
 #pragma unroll
@@ -685,58 +641,41 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
               }
             }
             if constexpr (IO16 && dx == 1 && g == NG / 2) {   // halo piece dy of chunk gc+2 (one per unit)
-              if (BF16S || more_in) issue_in_dma(dy, pb_in);
+              issue_in_dma(dy, pb_in);
             }
-            if constexpr (PIPE && !IO16 && dx >= 1 && g == NG / 2 && !(ABL & 4)) {   // split round R of the next chunk
+            if constexpr (PIPE && !IO16 && dx >= 1 && g == NG / 2) {   // split round R of the next chunk
               constexpr int R = dx >= 1 ? 2 * dy + dx - 1 : 0;
-              if (BF || has_next) {
-                if constexpr (dy == 0) {
-                  if (gc == 0) wait_vmcnt<0>();   // (chunk 1's raw pieces were issued by the prologue: no unit end since)
-                }
-                conv_split(rawr[R]);
-                conv_store(std::integral_constant<int, R>(), cnext);
-                if (BF || more_in) issue_in_piece(std::integral_constant<int, R>());
+              if constexpr (dy == 0) {
+                if (gc == 0) wait_vmcnt<0>();   // (chunk 1's raw pieces were issued by the prologue: no unit end since)
               }
+              conv_split(rawr[R]);
+              conv_store(std::integral_constant<int, R>(), cnext);
+              issue_in_piece(std::integral_constant<int, R>());
             }
-            if constexpr (!(ABL & 16) && !((ABL & 256) && dx == 2)) {   // (256: only two of the three taps' MFMAs -- what a Winograd F(2,3) would issue)
 #pragma unroll
-              for (int mt = 0; mt < MT; ++mt)
+            for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int nq = 0; nq < NT; ++nq) {
-                  const int nt = nq;
-                  const bf16x8 av = PR::W[g] < NPW ? A[set][PR::W[g] < NPW ? PR::W[g] : 0][mt] : Ad[mt];
-                  if constexpr (PR::F16)
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av),
-                                                                         __builtin_bit_cast(f16x8, Bq[set][PR::X[g]][nt]), acc[mt][nt], 0, 0, 0);
-                  else
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, Bq[set][PR::X[g]][nt], acc[mt][nt], 0, 0, 0);
-                }
-            }
+              for (int nt = 0; nt < NT; ++nt) {
+                const bf16x8 av = PR::W[g] < NPW ? A[set][PR::W[g] < NPW ? PR::W[g] : 0][mt] : Ad[mt];
+                if constexpr (PR::F16)
+                  acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, av),
+                                                                       __builtin_bit_cast(f16x8, Bq[set][PR::X[g]][nt]), acc[mt][nt], 0, 0, 0);
+                else
+                  acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, Bq[set][PR::X[g]][nt], acc[mt][nt], 0, 0, 0);
+              }
             __builtin_amdgcn_sched_barrier(0);
           });
-          if constexpr (dx == 0) {
-            if constexpr (BFA) issue_w_done(do_w);
-            else if (do_w) issue_w_done();
-          }
+          if constexpr (dx == 0) issue_w_done(do_w);
         });
-        if (!(ABL & 8)) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          // PIPE, steady state: the weights of unit u+1 (issued in unit u-1) landed, and with them every raw load older than
-          // unit u-1's; still in flight may be: raw(u-1) x 2, W(u+2) x NW_W, raw(u) x 2.  (vmcnt counts in issue order.)
-          if constexpr (BF && PIPE) {
-            wait_vmcnt<4 + NW_W>();   // (every unit issued its NW_W pieces and two loads, live or not: one constant count)
-          } else if constexpr (BF16S) {
-            wait_vmcnt<2 + NW_W>();   // (likewise: NW_W pieces and one halo piece per unit)
-          } else if (IO16 && more_in) {
-            wait_vmcnt<2 + NW_W>();   // in flight may be: halo piece of unit u-1, W(u+2) x NW_W, halo piece of unit u
-          } else if (PIPE && !IO16 && more_in) {
-            if ((ABL & 128) && c == 0 && dy == 0) wait_vmcnt<4 + NW_W + 16>();
-            else wait_vmcnt<4 + NW_W>();
-          } else wait_vmcnt<0>();
-          stamp(2 * (3 * c + dy));
-          __builtin_amdgcn_s_barrier();
-          stamp(2 * (3 * c + dy) + 1);
-        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // PIPE, steady state: the weights of unit u+1 (issued in unit u-1) landed, and with them every raw load older than
+        // unit u-1's; still in flight may be: raw(u-1) x 2, W(u+2) x NW_W, raw(u) x 2.  (vmcnt counts in issue order.)
+        if constexpr (IO16) {
+          wait_vmcnt<2 + NW_W>();   // (every unit issued its NW_W pieces and one halo piece, live or not: one constant count)
+        } else if constexpr (PIPE) {
+          wait_vmcnt<4 + NW_W>();   // (likewise: NW_W pieces and two loads per unit)
+        } else wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
         slot_cur = slot_cur == (unsigned)((NRING - 1) * WUNIT) ? 0u : slot_cur + (unsigned)WUNIT;
       });
     }
@@ -754,8 +693,8 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
     // column of tiles): a straight-line epilogue.  Row 0's eight residual pieces are requested HERE, in front of the
     // bias / activation arithmetic, row 1's before row 0 is stored.  (The generic path below fetches each piece behind its own branches
     // and between two stores that may alias it: hipcc serialises that into 16 x (load, s_waitcnt vmcnt(0), add, store), and on gfx9 that
-    // wait also drains the previous store -- 21 000 cycles per tile against 7 300 without a residual, scripts/trace_split.py.)
-    constexpr bool EPI_FAST = MODE == 0 && !IO16 && (ABL & (64 | 512)) == 0;
+    // wait also drains the previous store -- 21 000 cycles per tile against 7 300 without a residual)
+    constexpr bool EPI_FAST = MODE == 0 && !IO16;
     bool fast = false;
     size_t fpix = 0;
     f32x4 rv[MT][4];   // one pixel row's pieces at a time (both rows: 64 registers, and hipcc spills)
@@ -775,10 +714,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
     };
     // the same for bf16 tensors (configs[4]'s bodies: bf16 output, bf16 residual): both rows' four 16-byte pieces per lane, requested here
     typedef __bf16 bf16x8r __attribute__((ext_vector_type(8)));
-    constexpr bool EPI_FAST16 = IO16 && (ABL & (64 | 512)) == 0;   // (IO16 implies FL == 1, MODE == 0)
     bool fast16 = false;
     bf16x8r hres[NT][MT][2];
-    if constexpr (EPI_FAST16) {
+    if constexpr (IO16) {   // (implies FL == 1, MODE == 0)
       fast16 = (p.io_flags & 6) == 6 && p.res1 != nullptr && cb * MW + MW <= p.Cout && y0 + THY <= p.H && x0 + TWX <= p.W;
       if (fast16) {
         const __bf16* rb = reinterpret_cast<const __bf16*>(p.res1) + (size_t)b * p.out_img_pitch + (size_t)(y0 + 2 * wv) * p.out_row_pitch +
@@ -809,22 +747,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
             else acc[mt][nt][4 * qd + e] += bv[e];
           }
       }
-    if constexpr ((ABL & 64) != 0) {
-      // (ablation: one 16-byte store per lane and tile -- the sum of its accumulators -- instead of sixteen)
-      f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r & 3] += acc[mt][nt][r];
-      const int y = y0 + 2 * wv, x = x0 + j;
-      if (y < p.H && x < p.W) {
-        const size_t o = (size_t)b * p.out_img_pitch + (size_t)y * p.out_row_pitch + (size_t)x * p.out_pix_pitch + co_e;
-        if constexpr (IO16) *reinterpret_cast<f32x4*>(reinterpret_cast<__bf16*>(p.out) + 2 * (o / 2)) = v;   // (stays inside a bf16 tensor)
-        else *reinterpret_cast<f32x4*>(p.out + o) = v;
-      }
-    } else if constexpr (MODE == 3 || MODE == 5) {
+    if constexpr (MODE == 3 || MODE == 5) {
       float asum = 0.0f;
       const HeadOut ho = head_out(p, b);
       // MODE 5 (W % 4 == 0; $C2M_HEAD_QUAD=0 keeps MODE 3): 16-byte planar stores after a 4 x 4 transpose inside the lane
@@ -962,7 +885,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
                           for (int e = 0; e < 4; ++e) { v[e] += a[e]; v[4 + e] += c[e]; }
                         }
                       };
-                      if (EPI_FAST16 && fast16) {
+                      if (IO16 && fast16) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += (float)hres[nt][mt][k][e];
                       } else if (p.res1) res(p.res1, (p.io_flags & 4) != 0);
@@ -984,18 +907,6 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = acc[mt][nt][4 * qd + e];
-                if constexpr ((ABL & 512) != 0) {
-                  // (ablation: the ADDRESS pattern of quad-transposed stores -- lanes 4q .. 4q+3 write the four consecutive 16-byte
-                  // pieces of pixel 4q + qd -- with untransposed data: what would coalesced 64-byte runs per quad buy?)
-                  const int xq = x0 + 4 * (j >> 2) + qd, cq = cb * MW + mt * 32 + 4 * (4 * hi + (j & 3));
-                  if (xq < p.W && cq + 3 < p.Cout) {
-                    const size_t oq = (size_t)b * p.out_img_pitch + (size_t)y * p.out_row_pitch + (size_t)xq * p.out_pix_pitch + cq;
-                    if (p.res1) v += *reinterpret_cast<const f32x4*>(p.res1 + oq);
-                    if (p.res2) v += *reinterpret_cast<const f32x4*>(p.res2 + oq);
-                    *reinterpret_cast<f32x4*>(p.out + oq) = v;
-                  }
-                  continue;
-                }
                 if constexpr (FL == 1) {
                   // bf16 flavour: the output / the residuals may hold bf16 (Params::io_flags; Cout % 4 == 0 then) -- the sum
                   // is taken in fp32 and rounded once
@@ -1098,15 +1009,9 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.0f;
-    stamp(24);
   }
   if constexpr (FL == 2) {
     if (p.range_flag != nullptr && !(amax < 65520.0f)) *p.range_flag = 1;   // (rare, idempotent store; inf counts)
-  }
-  if constexpr ((ABL & 1024) != 0) {
-    const unsigned xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)), hwid = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_XCC_ID[3:0], HW_REG_HW_ID
-    asm volatile("v_writelane_b32 %0, %1, 62\n\tv_writelane_b32 %0, %2, 63" : "+v"(trace_v) : "s"(xcc), "s"(hwid));
-    reinterpret_cast<unsigned*>(p.mask_out)[((size_t)blockIdx.x * 4 + wv) * 64 + l] = trace_v;
   }
 }
 
@@ -1176,86 +1081,7 @@ static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid) {
         if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds16, dn)) == C2M_OK)
           hipLaunchKernelGGL(kern, grid, dim3(256), lds16, st, p);
       };
-      if constexpr (MT == 2) {   // (timing-only ablations, as for the f16 x 2 flavour: $C2M_SPLIT_ABL16)
-        static const int abl = [] {
-          const char* e = getenv("C2M_SPLIT_ABL16");
-          const int v = e ? atoi(e) : 0;
-          if (v > 0) fprintf(stderr, "c2m: C2M_SPLIT_ABL16=%d -- the bf16-tensor conv3x3 kernel runs a timing-only ablation, its results are wrong\n", v);
-          return v;
-        }();
-        static unsigned long long dn[9] = {};
-        switch (abl) {
-          case 0: break;
-          case 1: go16(&split::conv3x3_split_kernel<1, 2, 0, 1, true>, dn[0]); return rc;
-          case 2: go16(&split::conv3x3_split_kernel<1, 2, 0, 2, true>, dn[1]); return rc;
-          case 8: go16(&split::conv3x3_split_kernel<1, 2, 0, 8, true>, dn[2]); return rc;
-          case 16: go16(&split::conv3x3_split_kernel<1, 2, 0, 16, true>, dn[3]); return rc;
-          case 32: go16(&split::conv3x3_split_kernel<1, 2, 0, 32, true>, dn[4]); return rc;
-          case 64: go16(&split::conv3x3_split_kernel<1, 2, 0, 64, true>, dn[5]); return rc;
-          case 43: go16(&split::conv3x3_split_kernel<1, 2, 0, 43, true>, dn[6]); return rc;
-          case 48: go16(&split::conv3x3_split_kernel<1, 2, 0, 48, true>, dn[7]); return rc;
-          case 107: go16(&split::conv3x3_split_kernel<1, 2, 0, 107, true>, dn[8]); return rc;
-          default: fprintf(stderr, "c2m: unknown C2M_SPLIT_ABL16 mask\n"); return C2M_ERR_INVALID_ARG;
-        }
-      }
-      go16(&split::conv3x3_split_kernel<1, MT, 0, 0, true>, done16);
-      return rc;
-    }
-  }
-  if constexpr (NP == 2 && MT == 2) {   // (timing-only ablations exist for the f16 x 2 flavour on 64-wide cout tiles)
-    static const int abl = [] {
-      const char* e = getenv("C2M_SPLIT_ABL");
-      const int v = e ? atoi(e) : 0;
-      if (v > 0) fprintf(stderr, "c2m: C2M_SPLIT_ABL=%d -- conv3x3 split kernel runs a timing-only ablation, its results are wrong\n", v);
-      return v;
-    }();
-    static unsigned long long done_abl[13] = {};
-    if (abl > 0 && p.out_mode == 0) {
-      switch (abl) {
-        case 1: go(&split::conv3x3_split_kernel<NP, 2, 0, 1>, done_abl[1]); break;
-        case 2: go(&split::conv3x3_split_kernel<NP, 2, 0, 2>, done_abl[2]); break;
-        case 6: go(&split::conv3x3_split_kernel<NP, 2, 0, 6>, done_abl[3]); break;
-        case 8: go(&split::conv3x3_split_kernel<NP, 2, 0, 8>, done_abl[4]); break;
-        case 32: go(&split::conv3x3_split_kernel<NP, 2, 0, 32>, done_abl[5]); break;
-        case 39: go(&split::conv3x3_split_kernel<NP, 2, 0, 39>, done_abl[6]); break;
-        case 47: go(&split::conv3x3_split_kernel<NP, 2, 0, 47>, done_abl[7]); break;
-        case 48: go(&split::conv3x3_split_kernel<NP, 2, 0, 48>, done_abl[8]); break;
-        case 64: go(&split::conv3x3_split_kernel<NP, 2, 0, 64>, done_abl[9]); break;
-        case 128: go(&split::conv3x3_split_kernel<NP, 2, 0, 128>, done_abl[10]); break;
-        case 111: go(&split::conv3x3_split_kernel<NP, 2, 0, 111>, done_abl[11]); break;
-        case 112: go(&split::conv3x3_split_kernel<NP, 2, 0, 112>, done_abl[12]); break;
-        case 256: go(&split::conv3x3_split_kernel<NP, 2, 0, 256>, done_abl[0]); break;
-        case 512: { static unsigned long long d512 = 0; go(&split::conv3x3_split_kernel<NP, 2, 0, 512>, d512); break; }
-#ifdef C2M_SPLIT_TRACE
-        case 2048: { static unsigned long long d2048 = 0; go(&split::conv3x3_split_kernel<NP, 2, 0, 2048>, d2048); break; }
-        case 1024: {   // timeline build: RIGHT results; every launch appends [int grid][int tpw][grid x 4 x 64 words] to $C2M_SPLIT_TRACE_FILE
-          static unsigned long long d1024 = 0;
-          static unsigned* tbuf = nullptr;
-          const size_t tb = (size_t)grid.x * 4 * 64 * sizeof(unsigned);
-          if (!tbuf && hipMalloc(&tbuf, 4096 * 4 * 64 * sizeof(unsigned)) != hipSuccess) return C2M_ERR_LAUNCH;
-          if (grid.x > 4096) return C2M_ERR_UNSUPPORTED;
-          (void)hipMemsetAsync(tbuf, 0, tb, st);
-          Params q = p;
-          q.mask_out = reinterpret_cast<float*>(tbuf);
-          const char* e = getenv("C2M_SPLIT_TRACE_IT");
-          q.co_off = e ? atoi(e) : 20;
-          if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&split::conv3x3_split_kernel<NP, 2, 0, 1024>), ldsb, d1024)) == C2M_OK) {
-            hipLaunchKernelGGL((split::conv3x3_split_kernel<NP, 2, 0, 1024>), grid, dim3(256), ldsb, st, q);
-            const char* fn = getenv("C2M_SPLIT_TRACE_FILE");
-            if (fn) {
-              (void)hipStreamSynchronize(st);
-              unsigned* h = (unsigned*)malloc(tb);
-              (void)hipMemcpy(h, tbuf, tb, hipMemcpyDeviceToHost);
-              FILE* f = fopen(fn, "ab");
-              if (f) { const int hd[4] = {(int)grid.x, p.tpw, p.res1 != nullptr, p.H}; fwrite(hd, 4, 4, f); fwrite(h, 1, tb, f); fclose(f); }
-              free(h);
-            }
-          }
-          break;
-        }
-#endif
-        default: fprintf(stderr, "c2m: unknown C2M_SPLIT_ABL mask\n"); return C2M_ERR_INVALID_ARG;
-      }
+      go16(&split::conv3x3_split_kernel<1, MT, 0, true>, done16);
       return rc;
     }
   }

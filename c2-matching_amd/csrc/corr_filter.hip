@@ -274,17 +274,7 @@ __device__ __forceinline__ unsigned select_u32(unsigned long long lane_mask, uns
   return r;
 }
 
-// C2M_CORRF_ABL (compile-time, measurement builds only -- results are wrong with any bit set; scripts/abl_corr_filter.py):
-// 1 B operands read once per row and reused, 2 no ring reads in the tap rounds, 4 no tap rounds, 8 no row-sum tail (DPP + ring
-// stores), 16 no MFMAs.  Round 5, C = 256, 160 x 160 maps, B = 16, no skipped rows: 25.2 ms; 1: 24.1, 2: 23.6, 3: 22.5, 4: 20.9,
-// 8: 24.3, 15 (MFMAs + row DMA + barriers only): 18.7 = the pipe at the 1.42 GHz the chip holds under it; 16: 10.6.
-#ifndef C2M_CORRF_ABL
-#define C2M_CORRF_ABL 0
-#endif
-#ifndef C2M_CORRF_FAST
-#define C2M_CORRF_FAST 1
-#endif
-template <int C, int PF>
+template <int C>
 __global__ void __launch_bounds__(NTHR, 2) corr_filter_kernel(
     const _Float16* __restrict__ qpl, const _Float16* __restrict__ rimg, int Hq, int Wq, int Hr, int Wr, int tiles_y, int tiles_x,
     const float* __restrict__ sc, const float* __restrict__ band, const int2* __restrict__ skip, int* __restrict__ cnt,
@@ -393,37 +383,30 @@ __global__ void __launch_bounds__(NTHR, 2) corr_filter_kernel(
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
     const unsigned cur = code, curhi = code << 16;
 
-    // B operands: read PF k steps ahead into a ring of PF + 1 register sets
-    f16x8 b0[PF + 1], b1[PF + 1];
+    // B operands: read one k step ahead into the other of two register sets (two steps ahead measured equal on configs[2],
+    // 17.5 vs 17.6 ms, and leaves no register to spare at C = 256)
+    f16x8 b0[2], b1[2];
     float hq[3];
-#pragma unroll
-    for (int t = 0; t < PF; ++t) {
-      b0[t] = *reinterpret_cast<const f16x8*>(bsrc + t * 1024);
-      b1[t] = *reinterpret_cast<const f16x8*>(bsrc + (KS + t) * 1024);
-    }
+    b0[0] = *reinterpret_cast<const f16x8*>(bsrc);
+    b1[0] = *reinterpret_cast<const f16x8*>(bsrc + KS * 1024);
     hq[0] = a0[0]; hq[1] = a1[0]; hq[2] = a2[0];
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
-      if (!(C2M_CORRF_ABL & 16)) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[1][t], b0[t % (PF + 1)], acc, 0, 0, 0);   // smallest terms first
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[1][t], b0[t & 1], acc, 0, 0, 0);   // smallest terms first
       __builtin_amdgcn_sched_barrier(0);
-      if ((C2M_CORRF_ABL & 1) && t + PF < KS) {
-        b0[(t + PF) % (PF + 1)] = b0[t % (PF + 1)];
-        b1[(t + PF) % (PF + 1)] = b1[t % (PF + 1)];
-      } else if (t + PF < KS) {
-        b0[(t + PF) % (PF + 1)] = *reinterpret_cast<const f16x8*>(bsrc + (t + PF) * 1024);
-        b1[(t + PF) % (PF + 1)] = *reinterpret_cast<const f16x8*>(bsrc + (KS + t + PF) * 1024);
+      if (t + 1 < KS) {
+        b0[(t + 1) & 1] = *reinterpret_cast<const f16x8*>(bsrc + (t + 1) * 1024);
+        b1[(t + 1) & 1] = *reinterpret_cast<const f16x8*>(bsrc + (KS + t + 1) * 1024);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (!(C2M_CORRF_ABL & 16)) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[0][t], b1[t % (PF + 1)], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[0][t], b0[t % (PF + 1)], acc, 0, 0, 0);
-      }
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[0][t], b1[t & 1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa[0][t], b0[t & 1], acc, 0, 0, 0);
       // tap-sum rounds [t NIT / KS, (t+1) NIT / KS)
 #pragma unroll
-      for (int r = (C2M_CORRF_ABL & 4) ? NIT : t * NIT / KS; r < (t + 1) * NIT / KS; ++r) {
+      for (int r = t * NIT / KS; r < (t + 1) * NIT / KS; ++r) {
         float sum = hq[0] + hq[1];
         sum = sum + hq[2];
-        if (!(C2M_CORRF_ABL & 2) && r + 1 < NIT) {
+        if (r + 1 < NIT) {
           hq[0] = a0[(r + 1) * TQ * WT];
           hq[1] = a1[(r + 1) * TQ * WT];
           hq[2] = a2[(r + 1) * TQ * WT];
@@ -433,9 +416,9 @@ __global__ void __launch_bounds__(NTHR, 2) corr_filter_kernel(
         // values), and after the first few hundred candidates that is nearly every score -- so the update sits behind ONE compare and
         // a wave-uniform branch: 5 vector instructions per round instead of 13 when no lane of the wave improves.  On this chip a
         // wave's vector-ALU instructions cost matrix-pipe time whether or not another wave runs beside it, and
-        // the 14 rounds per ref row were a fifth of the sweep.  (C2M_CORRF_FAST=0: the unconditional update, for A/B builds.)
+        // the 14 rounds per ref row were a fifth of the sweep.
         const unsigned long long m3 = __builtin_amdgcn_fcmpf(v, v3[r], 2 /* ogt */);
-        if (!C2M_CORRF_FAST || m3 != 0ull) {
+        if (m3 != 0ull) {
           // (lane masks + explicit v_cndmask: left to itself hipcc turns the two selects into divergent branches)
           const unsigned long long m1 = __builtin_amdgcn_fcmpf(v, v1[r], 2 /* ogt */), m2 = __builtin_amdgcn_fcmpf(v, v2[r], 2);
           const unsigned pa = (pk[r] << 16) | cur, pb = (pk[r] & 0xffffu) | curhi;
@@ -456,10 +439,7 @@ __global__ void __launch_bounds__(NTHR, 2) corr_filter_kernel(
       return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130, 0xf, 0xf, true));
     };
     float hh[TPQ];
-    if (C2M_CORRF_ABL & 8) {
-#pragma unroll
-      for (int r = 0; r < TPQ; ++r) hh[r] = acc[r];
-    } else {
+    {
       float dv[16], tt[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) dv[r] = acc[r];
@@ -474,7 +454,7 @@ __global__ void __launch_bounds__(NTHR, 2) corr_filter_kernel(
     {
       float* dst = ring + sl0 * SLAB + store_off;
 #pragma unroll
-      for (int r = 0; r < ((C2M_CORRF_ABL & 8) ? 1 : TPQ); ++r) dst[r * WT] = hh[r];
+      for (int r = 0; r < TPQ; ++r) dst[r * WT] = hh[r];
     }
 
     if (xtn != xt) sk = skb[min(xtn, nxt - 1)];
@@ -681,11 +661,9 @@ static int launch_filter_c(hipStream_t st, const _Float16* qpl, const _Float16* 
                            const float* sc, const float* band, const int2* skip, int* cnt, int* cand) {
   const int tiles_y = ceil_div(Hq - 2, TPQ), tiles_x = ceil_div(Wq - 2, TPQ);
   const size_t lds = sizeof(float) * (size_t)(3 * SLAB) + 2 * (size_t)C * 128;
-  // operand prefetch distance in k steps ($C2M_CORR_PF = 2: two steps ahead -- measured equal to one step on configs[2], 17.5 vs 17.6 ms, and it leaves no register to spare at C = 256)
-  static const int pf = [] { const char* e = getenv("C2M_CORR_PF"); return (e && e[0] == '2') ? 2 : 1; }();
-  static unsigned long long lds_set[2] = {0, 0};
-  auto kern = pf == 1 ? &corr_filter_kernel<C, 1> : &corr_filter_kernel<C, 2>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set[pf - 1])) return rc;
+  static unsigned long long lds_set = 0;
+  auto kern = &corr_filter_kernel<C>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set)) return rc;
   ProfileScope prof(C2M_KERNEL_CORR_FILTER, st);
   hipLaunchKernelGGL(kern, dim3(B * tiles_y * tiles_x), dim3(NTHR), lds, st, qpl, rimg, Hq, Wq, Hr, Wr, tiles_y, tiles_x, sc, band,
                      skip, cnt, cand);

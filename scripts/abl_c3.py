@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel time of the 3 -> 64 first-layer kernel (HIP events, c2m_profile_*) for A/B builds ($C2M_LIB) and the compile-time
-ablations of conv3x3_c3_kernel (C2M_C3_ABL).  usage: abl_c3.py [B] [size]"""
+"""Kernel time of the 3 -> 64 first-layer kernel (HIP events, c2m_profile_*), of the in-tree library or an A/B build
+($C2M_LIB).  usage: abl_c3.py [B] [size] [twin]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "c2-matching_amd"))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel time of the correlation's filter sweep alone (HIP events, c2m_profile_*), for A/B builds ($C2M_LIB) and the
-compile-time ablations of corr_filter.hip (C2M_CORRF_ABL).  usage: abl_corr_filter.py [B] [size]"""
+"""Kernel time of the correlation's filter sweep alone (HIP events, c2m_profile_*), of the in-tree library or an A/B build
+($C2M_LIB).  usage: abl_corr_filter.py [B] [size]"""
 import os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "c2-matching_amd"))

@@ -44,3 +44,28 @@ def test_no_128_bit_buffer_store_with_a_register_soffset(disassembly):
     assert len(wide) > 100        # the channels-last epilogues are there
     reg = [s for s in wide if re.fullmatch(r"(s\d+|m0|vcc_lo|vcc_hi|ttmp\d+)", s)]
     assert not reg, f"{len(reg)} wide buffer stores with a register soffset: {sorted(set(reg))[:8]}"
+
+
+def test_no_measurement_scaffolding_in_the_shipped_library(tmp_path):
+    """The timing-only ablation variants and A/B knobs of rounds 3 to 6 are gone (their numbers live on in DESIGN.md and profiles/):
+    the library names none of their switches, and its code object holds the 38 product instantiations of conv3x3_split_kernel
+    -- 3 flavours x 2 cout widths x 6 output modes + 2 bf16-source kernels -- and nothing else of that name."""
+    if not os.path.exists(OBJDUMP):
+        pytest.skip("ROCm llvm-objdump not installed")
+    if not os.path.exists(LIB):
+        pytest.fail("libc2m_hip.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
+    blob = open(LIB, "rb").read()
+    for name in (b"C2M_SPLIT_ABL", b"C2M_CONV_ABL", b"C2M_CORR_PF", b"C2M_SPLIT_TRACE"):
+        assert name not in blob, f"{name.decode()} is back in libc2m_hip.so"
+    shutil.copy(LIB, tmp_path / "lib.so")
+    subprocess.run([OBJDUMP, "--offloading", "lib.so"], cwd=tmp_path, check=True, capture_output=True)
+    objs = sorted(f for f in os.listdir(tmp_path) if "amdgcn-amd-amdhsa--gfx950" in f)
+    assert objs, "no gfx950 code objects in the library"
+    kernels = set()
+    for f in objs:
+        out = subprocess.run([OBJDUMP, "-t", f], cwd=tmp_path, check=True, capture_output=True, text=True).stdout
+        for line in out.splitlines():
+            cols = line.split()
+            if len(cols) >= 4 and "F" in cols[1:-1] and ".text" in line and "conv3x3_split_kernel" in cols[-1]:
+                kernels.add(cols[-1])
+    assert len(kernels) == 38, f"{len(kernels)} conv3x3_split_kernel functions in the code object: {sorted(kernels)}"
