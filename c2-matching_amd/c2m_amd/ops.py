@@ -3,6 +3,13 @@
 Every function takes CUDA(=HIP) float32 tensors, enqueues hand-written gfx950 kernels from libc2m_hip.so on the
 current torch stream and returns freshly allocated tensors.  CPU tensors are rejected: there is no fallback path.
 """
+import collections
+import ctypes
+import os
+import threading
+import warnings
+import weakref
+
 import torch
 
 from . import _lib
@@ -136,7 +143,6 @@ class record_corr_skip_table:
 
 
 def _skip_table(ws, shp):
-    import ctypes
     off, nxt = ctypes.c_size_t(0), ctypes.c_int(0)
     _lib.check(_lib.lib().c2m_feature_match_skip_table(*shp, ctypes.byref(off), ctypes.byref(nxt)),
                "c2m_feature_match_skip_table")
@@ -145,7 +151,6 @@ def _skip_table(ws, shp):
 
 
 def _filter_tables(ws, shp, nq):
-    import ctypes
     c, k, f, slots = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int(0)
     _lib.check(_lib.lib().c2m_feature_match_filter_tables(*shp, ctypes.byref(c), ctypes.byref(k), ctypes.byref(f),
                                                           ctypes.byref(slots)), "c2m_feature_match_filter_tables")
@@ -195,44 +200,37 @@ class _apply_switch:
         return False
 
 
-class corr_filter_mode:
+class _switch_mode:
+    """Base of the two A/B context managers: records the mode process-wide while the block is open (see above)."""
+    which = None
+
+    def __init__(self, mode):
+        self.mode = int(mode)
+        if self.mode not in (0, 1):
+            raise _lib.C2MError(f"{type(self).__name__}: 0 or 1")
+
+    def __enter__(self):
+        self.prev = _switch_override[self.which]
+        _switch_override[self.which] = self.mode
+        return self
+
+    def __exit__(self, *exc):
+        _switch_override[self.which] = self.prev
+        return False
+
+
+class corr_filter_mode(_switch_mode):
     """`with ops.corr_filter_mode(0): ...` -- exact fp32 sweep only; (1): pre-filter + exact re-score (default); results are
     identical (c2m_feature_match_set_filter).  Applies to every thread's launches through this module while the block is open
     (measurement / tests)."""
-
-    def __init__(self, mode):
-        self.mode = int(mode)
-        if self.mode not in (0, 1):
-            raise _lib.C2MError("corr_filter_mode: 0 or 1")
-
-    def __enter__(self):
-        self.prev = _switch_override["filter"]
-        _switch_override["filter"] = self.mode
-        return self
-
-    def __exit__(self, *exc):
-        _switch_override["filter"] = self.prev
-        return False
+    which = "filter"
 
 
-class head_store_mode:
+class head_store_mode(_switch_mode):
     """`with ops.head_store_mode(0): ...` -- the DCN head epilogue's dword planar stores; (1): 16-byte stores through the quad
     transpose + flow window (default where W % 4 == 0); identical results (c2m_conv3x3_set_head_stores).  Applies to every
     thread's launches through this module while the block is open."""
-
-    def __init__(self, mode):
-        self.mode = int(mode)
-        if self.mode not in (0, 1):
-            raise _lib.C2MError("head_store_mode: 0 or 1")
-
-    def __enter__(self):
-        self.prev = _switch_override["head"]
-        _switch_override["head"] = self.mode
-        return self
-
-    def __exit__(self, *exc):
-        _switch_override["head"] = self.prev
-        return False
+    which = "head"
 
 
 def last_corr_skip_table():
@@ -327,8 +325,7 @@ def dcn_fuse_offsets(conv_out, pre_offset, deformable_groups, kernel_taps, abs_s
         pre_offset = _dev_f32(pre_offset, "pre_offset")
         if tuple(pre_offset.shape) != (B, K, H, W, 2):
             raise _lib.C2MError("pre_offset must be [B, K, H, W, 2]")
-    if abs_sum is not None and (abs_sum.dtype != torch.float64 or abs_sum.numel() < 256 or not abs_sum.is_cuda):
-        raise _lib.C2MError("abs_sum must be a float64 GPU tensor with 256 slots (C2M_ABS_SUM_SLOTS)")
+    _check_abs_sum(abs_sum)
     offset = torch.empty((B, 2 * dg * K, H, W), dtype=torch.float32, device=conv_out.device)
     mask = torch.empty((B, dg * K, H, W), dtype=torch.float32, device=conv_out.device)
     with torch.cuda.device(conv_out.device):
@@ -344,6 +341,32 @@ def dcn_fuse_offsets(conv_out, pre_offset, deformable_groups, kernel_taps, abs_s
 # 3x3 convolution, channels-last, fused epilogue (csrc/conv3x3.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
+
+# Kernel kinds = weight-cache slot keys.  The seven conv3x3 kinds are the rows of _KINDS (ALGO_IDS maps the public algo= names
+# to them); the two DCNv2 images share the slot shape (id, rows, kind) but have no row.
+K_DIRECT, K_WINO, K_WINO4, K_SPLIT, K_BF16, K_DGRAD, K_SPLIT16 = range(7)
+K_DCN, K_DCN16 = "dcn", "dcn16"
+# One row per conv3x3 kind: public algo= name (K_DGRAD, the data-gradient image of the bf16 x 3 kernel, has none),
+# c2m_conv3x3_desc.algo, family name of the flop counters (conv_flops_by_family), matrix flops executed per algorithmic
+# (direct-convolution) flop, pieces of its split image (0: not a split image), the C-ABI's size / re-layout entry points and
+# whether Cin and Cout swap roles in the image (the data-gradient convolution maps dY's Cout channels to dX's Cin)
+_Kind = collections.namedtuple("_Kind", "name algo family exec_factor pieces size_fn relayout_fn swap")
+_SPLIT_IMAGE = ("c2m_conv3x3_relayout_split_bytes", "c2m_conv3x3_relayout_split_f32", False)
+_KINDS = {
+    K_DIRECT: _Kind("direct", 0, "direct", 1.0, 0, "c2m_conv3x3_relayout_bytes", "c2m_conv3x3_relayout_f32", False),
+    K_WINO: _Kind("winograd", 1, "winograd_f23", 2.0 / 3.0, 0, "c2m_conv3x3_relayout_wino_bytes", "c2m_conv3x3_relayout_wino_f32", False),
+    K_WINO4: _Kind("winograd4", 2, "winograd_f43", 0.5, 0, "c2m_conv3x3_relayout_wino4_bytes", "c2m_conv3x3_relayout_wino4_f32", False),
+    K_SPLIT: _Kind("split", 3, "split_bf16x3", 6.0, 3, *_SPLIT_IMAGE),
+    K_BF16: _Kind("bf16", 4, "bf16", 1.0, 1, *_SPLIT_IMAGE),
+    K_DGRAD: _Kind(None, 3, "dgrad_split_bf16x3", 6.0, 3, "c2m_conv3x3_relayout_split_bytes", "c2m_conv3x3_relayout_split_dgrad_f32", True),
+    K_SPLIT16: _Kind("split16", 5, "split_f16x2", 3.0, 2, *_SPLIT_IMAGE),
+}
+ALGO_IDS = {k.name: i for i, k in _KINDS.items() if k.name}
+_SPLIT_KINDS = (K_SPLIT, K_BF16, K_SPLIT16)      # the split kernel's three forward flavours
+_MFMA32_KINDS = (K_DIRECT, K_WINO, K_WINO4)      # the fp32-MFMA kernels
+_POOL_KINDS = (K_WINO,) + _SPLIT_KINDS           # kernels with the pooled epilogue (out_mode "nhwc_pool2")
+
+
 class _ConvFlops:
     """Opt-in FLOP accounting of the conv3x3 launches (bench.py's roofline line): off on the product path -- nothing is
     counted and no module state is written unless a caller enabled it with count_conv_flops(True)."""
@@ -384,6 +407,16 @@ def conv_flops_by_family():
     return {k: list(v) for k, v in (_ConvFlops.by_algo or {}).items()}
 
 
+def _cout_tiles(cout):
+    """The library's output-channel tile rule (csrc/conv3x3_shared.h cout_tiles): one 32-row tile for Cout <= 32, else two."""
+    return 1 if cout <= 32 else 2
+
+
+def _split_job_flags(k, cout):
+    """Flags word of one c2m_conv3x3_relayout_split_multi job: pieces | tiles << 8 | data-gradient image << 16."""
+    return k.pieces | (_cout_tiles(cout) << 8) | (int(k.swap) << 16)
+
+
 class _WeightCache:
     """Re-laid-out conv weights, keyed by the parameter tensor and its version counter: inference re-uses them across
     calls; an optimiser step (in-place update -> new _version) or load_state_dict invalidates them.  An entry belongs to
@@ -397,7 +430,6 @@ class _WeightCache:
     forward that uses it; ``clear()`` drops everything (clear_weight_caches)."""
 
     def __init__(self):
-        import threading
         self._d = {}
         self._tables = {}    # refresh job tables: frozenset(param ids) | None -> (signature, device int64 [n, 8], nblocks, any_f16)
         # nn.DataParallel runs the fused forwards of its replicas on one Python thread per GPU: every access to the two
@@ -412,7 +444,6 @@ class _WeightCache:
         return None
 
     def _store(self, slot, key, weight, value, redo=None):
-        import weakref
         d, lock = self._d, self._lock
 
         def _drop(ref, slot=slot):
@@ -446,18 +477,17 @@ class _WeightCache:
                 continue
             if key[0] != w.data_ptr() or key[1] != w._version:
                 continue        # stale by key: the next get() rebuilds it anyway
-            rows, kind = (slot[1], slot[2]) if isinstance(slot, tuple) and len(slot) == 3 else (None, None)
+            _, rows, kind = slot if len(slot) == 3 else (None, None, None)   # (id, rows, kind); anything else: redo only
             if kinds is not None and kind is not None and kind not in kinds:
                 continue
-            pieces = _KINDS[kind].pieces if isinstance(kind, int) else 0   # (the DCN cache's slots are not conv3x3 kinds)
-            if pieces and len(key) == 5 and key[3] is None and w.is_contiguous() and (dev is None or dev == w.device):
+            k = _KINDS.get(kind)      # (None: a DCNv2 image)
+            if k is not None and k.pieces and len(key) == 5 and key[3] is None and w.is_contiguous() and (dev is None or dev == w.device):
                 dev = w.device
                 Co, Ci = (rows[1] - rows[0] if rows is not None else w.shape[0]), w.shape[1]
-                cin_k, cout_k = (Co, Ci) if kind == 5 else (Ci, Co)      # the data-gradient conv swaps the roles
-                nbytes = _lib.lib().c2m_conv3x3_relayout_split_bytes(cin_k, cout_k, pieces) - (256 if pieces == 2 else 0)
+                cin_k, cout_k = (Co, Ci) if k.swap else (Ci, Co)
+                nbytes = _lib.lib().c2m_conv3x3_relayout_split_bytes(cin_k, cout_k, k.pieces) - (256 if k.pieces == 2 else 0)
                 wptr = w.data_ptr() + (rows[0] * Ci * 9 * 4 if rows is not None else 0)
-                jobs.append((wptr, value.data_ptr(), cin_k, cout_k, pieces | ((1 if cout_k <= 32 else 2) << 8) | ((1 if kind == 5 else 0) << 16),
-                             nbytes // 2))
+                jobs.append((wptr, value.data_ptr(), cin_k, cout_k, _split_job_flags(k, cout_k), nbytes // 2))
                 sig.append((slot, wptr, value.data_ptr()))
             else:
                 redo(w, value)
@@ -496,31 +526,19 @@ class _WeightCache:
             w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, pad_cin_to - Ci))
             Ci = pad_cin_to
         w = w.contiguous()
-        L = _lib.lib()
-        kind = int(kind)
-        pieces = _KINDS[kind].pieces
-        if pieces:   # split images (3 exact bf16 pieces / 1 rounded piece per weight / scaled f16 x 2); kind 5: of the data-gradient conv
-            nbytes = L.c2m_conv3x3_relayout_split_bytes(Co, Ci, pieces) if kind == 5 else L.c2m_conv3x3_relayout_split_bytes(Ci, Co, pieces)
-        else:
-            nbytes = (L.c2m_conv3x3_relayout_bytes, L.c2m_conv3x3_relayout_wino_bytes, L.c2m_conv3x3_relayout_wino4_bytes)[kind](Ci, Co)
+        L, k = _lib.lib(), _KINDS[kind]
+        args = ((Co, Ci) if k.swap else (Ci, Co)) + ((k.pieces,) if k.pieces else ())   # split images: + the number of pieces
+        nbytes = getattr(L, k.size_fn)(*args)
         if nbytes == 0:
             raise _lib.C2MError(f"conv3x3: unsupported channel counts Cin={Ci}, Cout={Co}" + (" for this kernel" if kind else
                                 " (input channels must be a multiple of 32)"))
         if wr is None:
             wr = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=w.device)
         with torch.cuda.device(w.device):
-            if kind == 5:
-                _lib.check(L.c2m_conv3x3_relayout_split_dgrad_f32(_stream(), w.data_ptr(), Ci, Co, pieces, wr.data_ptr()),
-                           "c2m_conv3x3_relayout_split_dgrad_f32")
-            elif pieces:
-                _lib.check(L.c2m_conv3x3_relayout_split_f32(_stream(), w.data_ptr(), Ci, Co, pieces, wr.data_ptr()),
-                           "c2m_conv3x3_relayout_split_f32")
-            else:
-                fn = (L.c2m_conv3x3_relayout_f32, L.c2m_conv3x3_relayout_wino_f32, L.c2m_conv3x3_relayout_wino4_f32)[kind]
-                _lib.check(fn(_stream(), w.data_ptr(), Ci, Co, wr.data_ptr()), "c2m_conv3x3_relayout")
+            _lib.check(getattr(L, k.relayout_fn)(_stream(), w.data_ptr(), Ci, Co, *args[2:], wr.data_ptr()), k.relayout_fn)
         return wr
 
-    def get(self, weight, pad_cin_to=None, rows=None, kind=0):   # kind: a row of _KINDS
+    def get(self, weight, pad_cin_to=None, rows=None, kind=K_DIRECT):   # kind: a row of _KINDS
         key = (weight.data_ptr(), weight._version, tuple(weight.shape), pad_cin_to, weight.device.index)
         slot = (id(weight), rows, kind)
         hit = self._lookup(slot, key, weight)
@@ -559,21 +577,18 @@ def empty_nhwc(B, C, H, W, device, dtype=torch.float32):
     return torch.empty((B, C, H, W), dtype=dtype, device=device, memory_format=torch.channels_last)
 
 
-import collections as _collections
-import os as _os
-
-_WINO = _os.environ.get("C2M_CONV_WINO", "1") != "0"
-_WINO4 = _os.environ.get("C2M_CONV_WINO4", "1") != "0"
+_WINO = os.environ.get("C2M_CONV_WINO", "1") != "0"
+_WINO4 = os.environ.get("C2M_CONV_WINO4", "1") != "0"
 # C2M_CONV_SPLIT: "all" (default) -- every convolution the split-bf16 kernel supports runs on it (csrc/conv3x3_split.hip:
 # fp32-accurate, 6 bf16 MFMAs per fp32 product sum), the extractor towers that feed the index search included (measured on
 # configs[2]: 1 near-tie flip of 24 964 queries against the CPU chain, 2 with the fp32-MFMA kernels); "1" -- only calls
 # with fast=True (decoder, DCN heads, VGG taps of the Ref); "0" -- never (fp32-MFMA direct / Winograd kernels only)
-_SPLIT = _os.environ.get("C2M_CONV_SPLIT", "all")
+_SPLIT = os.environ.get("C2M_CONV_SPLIT", "all")
 # C2M_CONV_SPLIT16: "1" (default) -- where the split kernel is chosen automatically, inference runs its f16 x 2 flavour
 # (three f16 products per fp32 product sum instead of six bf16 ones; error of the class of an fp32 accumulation chain,
 # domain |x| < 65520: include/c2m_hip.h C2M_CONV_SPLIT_F16X2); "0" -- the bf16 x 3 flavour (full fp32 range) everywhere.
 # The autograd path (conv3x3_autograd: gradients can be tiny) always runs bf16 x 3.
-_SPLIT16 = _os.environ.get("C2M_CONV_SPLIT16", "1") != "0"
+_SPLIT16 = os.environ.get("C2M_CONV_SPLIT16", "1") != "0"
 
 
 def experimental_built():
@@ -582,19 +597,7 @@ def experimental_built():
 
 
 # C2M_DCN_F16X2: "1" (default) -- the DCNv2 forward's implicit GEMM follows the convolutions onto the f16 x 2 arithmetic
-_DCN_F16X2 = _os.environ.get("C2M_DCN_F16X2", "1") != "0"
-# conv3x3 kernel kinds (= weight-cache slot keys), one row each: public algo= name (kind 5, the data-gradient image of the
-# bf16 x 3 kernel, has none), c2m_conv3x3_desc.algo, family name of the flop counters (conv_flops_by_family), matrix flops
-# executed per algorithmic (direct-convolution) flop, pieces of its c2m_conv3x3_relayout_split_f32 image (0: not a split image)
-_Kind = _collections.namedtuple("_Kind", "name algo family exec_factor pieces")
-_KINDS = (_Kind("direct", 0, "direct", 1.0, 0),
-          _Kind("winograd", 1, "winograd_f23", 2.0 / 3.0, 0),
-          _Kind("winograd4", 2, "winograd_f43", 0.5, 0),
-          _Kind("split", 3, "split_bf16x3", 6.0, 3),
-          _Kind("bf16", 4, "bf16", 1.0, 1),
-          _Kind(None, 3, "split_bf16x3", 6.0, 3),
-          _Kind("split16", 5, "split_f16x2", 3.0, 2))
-ALGO_IDS = {k.name: i for i, k in enumerate(_KINDS) if k.name}
+_DCN_F16X2 = os.environ.get("C2M_DCN_F16X2", "1") != "0"
 
 
 # ---- f16 x 2 is the DEFAULT arithmetic of fp32 inference, and its domain is |activation| < 65520: outside it the kernel
@@ -602,11 +605,9 @@ ALGO_IDS = {k.name: i for i, k in enumerate(_KINDS) if k.name}
 # inputs into a per-device flag (c2m_conv3x3_desc.range_flag), and the fused module forwards run under `f16_range_guard`: the
 # flag is zeroed before, read once after (one 4-byte read-back per module forward), and if it is set the forward is repeated
 # on the bf16 x 3 flavour (full fp32 exponent range) -- the module is then pinned to that flavour.
-import threading as _threading
-
-_tls = _threading.local()
+_tls = threading.local()
 _range_flags = {}
-_range_lock = _threading.Lock()
+_range_lock = threading.Lock()
 
 
 def _device_flag(dev):
@@ -631,12 +632,6 @@ def _range_flag(dev):
     return _device_flag(dev)
 
 
-def _split16_now():
-    """f16 x 2 (True) or bf16 x 3 (False) for an fp32 split-kernel call of this thread right now."""
-    ov = getattr(_tls, "flavour", None)
-    return _SPLIT16 if ov is None else ov
-
-
 def _f16x2_auto():
     """What algo=None resolves to in conv3x3 / conv3x3_dcn_head / dcn_v2_forward_nhwc: the f16 x 2 arithmetic only where
     somebody reads the range flag afterwards -- inside an f16_range_guard (the fused module forwards) -- or where the caller
@@ -650,7 +645,6 @@ def _f16x2_auto():
     if _SPLIT16 and not _f16x2_auto.warned and not torch.cuda.is_current_stream_capturing():
         #  say it once: $C2M_CONV_SPLIT16=1 does NOT make a bare call f16 x 2 -- about twice the matrix work
         _f16x2_auto.warned = True
-        import warnings
         warnings.warn("c2m_amd.ops: a conv3x3 / conv3x3_dcn_head / dcn_v2_forward_nhwc call outside `f16_range_guard` and without "
                       "`ops.conv_flavour(...)` runs the FULL-RANGE arithmetic (bf16 x 3 convolutions, fp32-MFMA DCNv2: ~2x the matrix "
                       "work of the f16 x 2 default of the fused module forwards).  For f16 x 2 wrap the calls in "
@@ -700,10 +694,11 @@ def f16_range_guard(owner, fn, device):
         return fn()
     # (under bf16 autocast the convolutions run the bf16 flavour and never touch the flag; the DCNv2 forwards -- fp32 under
     # autocast, as the reference's custom_fwd(cast_inputs=float32) makes them -- still run f16 x 2 and do)
-    if getattr(owner, "_c2m_conv_bf16x3", False) or not _split16_now():
-        if getattr(owner, "_c2m_conv_bf16x3", False):
-            with conv_flavour("bf16x3"):
-                return fn()
+    if getattr(owner, "_c2m_conv_bf16x3", False):
+        with conv_flavour("bf16x3"):
+            return fn()
+    ov = getattr(_tls, "flavour", None)
+    if not (_SPLIT16 if ov is None else ov):     # this thread's fp32 split-kernel calls run bf16 x 3 anyway: nothing to guard
         return fn()
     if torch.cuda.is_current_stream_capturing():
         # the range check reads a flag back, which a hipGraph capture cannot do: captured forwards run the full-range flavour
@@ -717,7 +712,6 @@ def f16_range_guard(owner, fn, device):
         _tls.guarded, _tls.guard_flag = False, None
     if int(flag.item()) == 0:
         return out
-    import warnings
     warnings.warn(f"{type(owner).__name__}: an activation left the f16 x 2 convolution flavour's domain (|x| >= 65520); the forward "
                   "was recomputed on the bf16 x 3 flavour (full fp32 range), which this module now keeps", RuntimeWarning)
     try:
@@ -752,6 +746,57 @@ def _split_ok(srcs, weight, fast):
             sum(s.shape[1] for s in srcs) == weight.shape[1])
 
 
+def _as_list(srcs):
+    return list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+
+
+def _check_abs_sum(abs_sum):
+    if abs_sum is not None and (abs_sum.dtype != torch.float64 or abs_sum.numel() < 256 or not abs_sum.is_cuda):
+        raise _lib.C2MError("abs_sum must be a float64 GPU tensor with 256 slots (C2M_ABS_SUM_SLOTS)")
+
+
+def _split_kind(algo):
+    """The split kernel's flavour for `algo` (None: automatic): one rounded bf16 piece if asked for by name or under bf16
+    autocast, else f16 x 2 if asked for by name or -- automatic only -- where somebody reads the range flag (_f16x2_auto, which
+    is not consulted, and does not warn, once autocast has decided), else bf16 x 3."""
+    if algo == "bf16" or (algo is None and bf16_autocast()):
+        return K_BF16
+    if algo == "split16" or (algo is None and _f16x2_auto()):
+        return K_SPLIT16
+    return K_SPLIT
+
+
+def _conv_desc(kind, srcs, wr, B, H, W, Cin, Cout, names=None, bf16_ok=False):
+    """A c2m_conv3x3_desc with the algo, geometry, sources, weight image and (f16 x 2) range flag of one launch filled in."""
+    d = _lib.Conv3x3Desc()
+    d.algo = _KINDS[kind].algo
+    d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cin, Cout, len(srcs)
+    for k, s in enumerate(srcs):
+        if tuple(s.shape[2:]) != (H, W) or s.shape[0] != B:
+            raise _lib.C2MError("conv3x3: sources must share B, H, W")
+        d.src[k] = _nhwc_src(s, names[k] if names else f"src{k}", bf16_ok=bf16_ok)
+    d.wr = wr.data_ptr()
+    if kind == K_SPLIT16:
+        d.range_flag = _range_flag(srcs[0].device).data_ptr()
+    return d
+
+
+def _desc_out(d, out, bf16_ok=False):
+    """Point the descriptor's output at a channels-last tensor; -> its ConvSrc (pitches)."""
+    o = _nhwc_src(out, "out", bf16_ok=bf16_ok)
+    d.out, d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch
+    return o
+
+
+def _launch_conv(d, dev, kind, family_prefix=""):
+    """c2m_conv3x3_nhwc_f32 on the current stream of `dev` (+ the opt-in flop accounting of the launch)."""
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
+    if _ConvFlops.enabled:
+        f = 2.0 * d.Cout * 9 * d.Cin * d.H * d.W * d.B
+        _ConvFlops.add(family_prefix + _KINDS[kind].family, f, f * _KINDS[kind].exec_factor)
+
+
 def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=None, out_mode="nhwc", out=None, algo=None,
             out2_grouped8=None, fast=False, out_dtype=None, dword_stores=False):
     """out = act(conv3x3(cat(srcs, dim=1)) + bias) + res1 + res2 on channels-last tensors, one kernel.
@@ -778,7 +823,7 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     $C2M_CONV_SPLIT=1 restricts it to calls with fast=True (the decoder; the extractor towers that feed the index search
     then stay on the fp32-MFMA kernels), $C2M_CONV_SPLIT=0 restores the round-2 choice everywhere: Winograd F(4,3) with
     fast=True / F(2,3) where the shapes allow, else direct."""
-    srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+    srcs = _as_list(srcs)
     B, _, H, W = srcs[0].shape
     Cin = sum(s.shape[1] for s in srcs)
     Cout = weight.shape[0]
@@ -787,9 +832,9 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
         reduced = bf16_autocast()
         if (out2_grouped8 is None and (_split_ok(srcs, weight, fast) or (reduced and _split_ok(srcs, weight, True))) and (out_mode != "nhwc_pool2" or (H % 2 == 0 and W % 2 == 0))
                 and (out_mode not in ("nhwc", "nhwc_pool2") or Cout % 4 == 0)):   # channels-last stores are 16-byte vectors
-            kind = 4 if reduced else 6 if _f16x2_auto() else 3
+            kind = _split_kind(None)
         else:
-            kind = 2 if (fast and _wino4_ok(srcs, weight, out_mode, W)) else 1 if _wino_ok(srcs, weight, out_mode, W) else 0
+            kind = K_WINO4 if (fast and _wino4_ok(srcs, weight, out_mode, W)) else K_WINO if _wino_ok(srcs, weight, out_mode, W) else K_DIRECT
     elif algo in ALGO_IDS:
         kind = ALGO_IDS[algo]
     else:
@@ -797,15 +842,9 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     if out2_grouped8 is not None:
         if algo not in (None, "direct") or out_mode != "nhwc":
             raise _lib.C2MError("out2_grouped8 needs the direct kernel in nhwc mode")
-        kind = 0
+        kind = K_DIRECT
     wr = _wcache.get(weight, pad_cin_to=Cin if weight.shape[1] < Cin else None, kind=kind)
-    d = _lib.Conv3x3Desc()
-    d.algo = _KINDS[kind].algo
-    d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cin, Cout, len(srcs)
-    for k, s in enumerate(srcs):
-        if tuple(s.shape[2:]) != (H, W) or s.shape[0] != B:
-            raise _lib.C2MError("conv3x3: sources must share B, H, W")
-        d.src[k] = _nhwc_src(s, f"src{k}", bf16_ok=True)
+    d = _conv_desc(kind, srcs, wr, B, H, W, Cin, Cout, bf16_ok=True)
     io = 1 if srcs[0].dtype == torch.bfloat16 else 0
     if any(s.dtype == torch.bfloat16 for s in srcs[1:]) or (io and len(srcs) != 1):
         raise _lib.C2MError("conv3x3: a bfloat16 source must be the only source")
@@ -818,14 +857,13 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     for bit, r in ((4, res1), (8, res2)):
         if r is not None and r.dtype == torch.bfloat16:
             io |= bit
-    if io and (kind != 4 or out_mode != "nhwc"):
+    if io and (kind != K_BF16 or out_mode != "nhwc"):
         raise _lib.C2MError("conv3x3: bfloat16 tensors need the bf16 kernel (algo='bf16' / bf16 autocast) in nhwc mode")
     if dword_stores:
-        if io or kind not in (3, 4, 6) or out_mode not in ("pixel_shuffle", "nchw"):
+        if io or kind not in _SPLIT_KINDS or out_mode not in ("pixel_shuffle", "nchw"):
             raise _lib.C2MError("conv3x3: dword_stores selects a store path of the split kernels' pixel_shuffle / nchw epilogues")
         io = 16
     d.io_flags = io
-    d.wr = wr.data_ptr()
     if bias is not None:
         bias = _dev_f32(bias.detach(), "bias")
     d.bias = bias.data_ptr() if bias is not None else None
@@ -834,8 +872,7 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
         if out is None:
             out = empty_nhwc(B, Cout, H, W, dev, torch.bfloat16 if io & 2 else torch.float32)
         d.out_mode = 0
-        o = _nhwc_src(out, "out", bf16_ok=True)
-        d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = o.pix_pitch, o.row_pitch, o.img_pitch
+        o = _desc_out(d, out, bf16_ok=True)
         for name, r in (("res1", res1), ("res2", res2)):
             if r is not None:
                 rs = _nhwc_src(r, name, bf16_ok=True)
@@ -847,28 +884,20 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     elif out_mode == "pixel_shuffle":
         out = empty_nhwc(B, Cout // 4, 2 * H, 2 * W, dev)
         d.out_mode = 1
-        o = _nhwc_src(out, "out")
-        d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = o.pix_pitch, o.row_pitch, o.img_pitch
+        _desc_out(d, out)
     elif out_mode == "nhwc_pool2":
-        if kind not in (1, 3, 4, 6) or H % 2 != 0 or W % 2 != 0:
+        if kind not in _POOL_KINDS or H % 2 != 0 or W % 2 != 0:
             raise _lib.C2MError("conv3x3: the pooled epilogue needs the Winograd F(2,3) or the split-bf16 kernel and even H, W")
         out = empty_nhwc(B, Cout, H // 2, W // 2, dev)
         d.out_mode = 4
-        o = _nhwc_src(out, "out")
-        d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = o.pix_pitch, o.row_pitch, o.img_pitch
+        _desc_out(d, out)
     elif out_mode == "nchw":
         out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=dev)
         d.out_mode = 2
+        d.out = out.data_ptr()
     else:
         raise _lib.C2MError(f"unknown out_mode {out_mode}")
-    d.out = out.data_ptr()
-    if kind == 6:
-        d.range_flag = _range_flag(dev).data_ptr()
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
-    if _ConvFlops.enabled:
-        f = 2.0 * Cout * 9 * Cin * H * W * B
-        _ConvFlops.add(_KINDS[kind].family, f, f * _KINDS[kind].exec_factor)
+    _launch_conv(d, dev, kind)
     return out
 
 
@@ -879,28 +908,19 @@ def conv3x3_dgrad(grad_out, weight):
     B, Cg, H, W = grad_out.shape
     if Cg != Cout or Cout % 16 != 0 or Cin % 4 != 0:
         raise _lib.C2MError("conv3x3_dgrad: grad_out channels must equal weight.shape[0] (a multiple of 16); Cin % 4 == 0")
-    wr = _wcache.get(weight, kind=5)
+    wr = _wcache.get(weight, kind=K_DGRAD)
     out = empty_nhwc(B, Cin, H, W, grad_out.device)
-    d = _lib.Conv3x3Desc()
-    d.algo = _KINDS[5].algo
-    d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cout, Cin, 1
-    d.src[0] = _nhwc_src(grad_out, "grad_out")
-    d.wr = wr.data_ptr()
+    d = _conv_desc(K_DGRAD, [grad_out], wr, B, H, W, Cout, Cin, names=("grad_out",))   # the convolution maps Cout to Cin channels
     d.out_mode = 0
-    o = _nhwc_src(out, "out")
-    d.out, d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch
-    with torch.cuda.device(grad_out.device):
-        _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32 (dgrad)")
-    if _ConvFlops.enabled:
-        f = 2.0 * Cout * 9 * Cin * H * W * B
-        _ConvFlops.add("dgrad_split_bf16x3", f, f * 6.0)
+    _desc_out(d, out)
+    _launch_conv(d, grad_out.device, K_DGRAD)
     return out
 
 
 def conv3x3_wgrad(srcs, grad_out, Cout):
     """Weight gradient of conv3x3(cat(srcs)): srcs / grad_out channels-last -> grad_weight [Cout, Cin, 3, 3] (fp32 MFMA over
     pixel segments, deterministic two-stage reduction; csrc/conv3x3_wgrad.hip)."""
-    srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+    srcs = _as_list(srcs)
     B, _, H, W = srcs[0].shape
     Cin = sum(s_.shape[1] for s_ in srcs)
     if tuple(grad_out.shape) != (B, Cout, H, W):
@@ -973,14 +993,14 @@ class _Conv3x3Fn(torch.autograd.Function):
 def conv3x3_autograd(srcs, weight, bias=None, act=ACT_NONE, slope=0.1):
     """act(conv3x3(cat(srcs)) + bias) with gradients (channels-last float32 in and out; sources a multiple of 32 channels,
     Cout a multiple of 16).  See _Conv3x3Fn."""
-    srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+    srcs = _as_list(srcs)
     return _Conv3x3Fn.apply(weight, bias, int(act), float(slope), *srcs)
 
 
 def conv3x3_autograd_ok(srcs, weight):
     """Shapes the differentiable path supports: 32-channel source blocks (weight-gradient kernel) and 16-byte channels-last
     output vectors (Cout % 4 == 0; the data-gradient convolution pads Cout to a multiple of 16 itself)."""
-    srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+    srcs = _as_list(srcs)
     return (all(s_.is_cuda and s_.dim() == 4 and s_.shape[1] % 32 == 0 for s_ in srcs) and weight.shape[0] % 4 == 0 and
             sum(s_.shape[1] for s_ in srcs) == weight.shape[1] and tuple(weight.shape[2:]) == (3, 3) and _SPLIT != "0")
 
@@ -1051,7 +1071,7 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
     flow: index_to_flow(max_idx) of the matched LR features (or None: no pre-offset); scale = H / h (1, 2, 4).
     The head's channels are computed in slices of 64-channel tiles + one 32-wide remainder (216 = 192 + 24) so that
     no padded tile is multiplied."""
-    srcs = list(srcs) if isinstance(srcs, (list, tuple)) else [srcs]
+    srcs = _as_list(srcs)
     B, _, H, W = srcs[0].shape
     Cin = sum(s.shape[1] for s in srcs)
     dg = int(deformable_groups)
@@ -1066,27 +1086,18 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
         if flow.dtype != torch.float32 or not flow.is_cuda or flow.dim() != 4 or flow.shape[0] != B or flow.shape[3] != 2:
             raise _lib.C2MError("flow must be float32 [B, fh, fw, 2] on the GPU")
         flow = flow.contiguous()
-    if abs_sum is not None and (abs_sum.dtype != torch.float64 or abs_sum.numel() < 256 or not abs_sum.is_cuda):
-        raise _lib.C2MError("abs_sum must be a float64 GPU tensor with 256 slots (C2M_ABS_SUM_SLOTS)")
+    _check_abs_sum(abs_sum)
     split = (Cout // 64) * 64
     slices = [(0, Cout)] if (split == 0 or Cout - split > 32 or split == Cout) else [(0, split), (split, Cout)]
     use_split = algo in ("split", "bf16", "split16") or (algo is None and _SPLIT != "0" and all(s_.shape[1] % 16 == 0 for s_ in srcs))
-    split_id = (4 if (algo == "bf16" or (algo is None and bf16_autocast())) else
-                6 if (algo == "split16" or (algo is None and _f16x2_auto())) else 3)
-    fam = []
+    split_kind = _split_kind(algo)
+    wino = _WINO and algo is None and W % 32 == 0 and all(s_.shape[1] % 16 == 0 for s_ in srcs)
     for (c0, c1) in slices:
         # split-bf16 kernel (any shape); else 64-channel-tileable slices on whole 32-pixel tiles take the Winograd F(2,3)
         # kernel (1.5x fewer matrix instructions), the rest the direct kernel
-        kind = split_id if use_split else int(_WINO and algo is None and (c1 - c0) % 64 == 0 and W % 32 == 0 and
-                                       all(s_.shape[1] % 16 == 0 for s_ in srcs))
-        fam.append(kind)
+        kind = split_kind if use_split else K_WINO if (wino and (c1 - c0) % 64 == 0) else K_DIRECT
         wr = _wcache.get(weight, rows=(c0, c1), kind=kind)
-        d = _lib.Conv3x3Desc()
-        d.algo = _KINDS[kind].algo
-        d.B, d.H, d.W, d.Cin, d.Cout, d.nsrc = B, H, W, Cin, c1 - c0, len(srcs)
-        for k, s in enumerate(srcs):
-            d.src[k] = _nhwc_src(s, f"src{k}")
-        d.wr = wr.data_ptr()
+        d = _conv_desc(kind, srcs, wr, B, H, W, Cin, c1 - c0)
         d.bias = bias.data_ptr() + 4 * c0
         d.out_mode = 3
         d.out, d.mask_out, d.n_off, d.scale = offset.data_ptr(), mask.data_ptr(), 2 * dg * 9, int(scale)
@@ -1095,14 +1106,8 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
             d.flow, d.fh, d.fw = flow.data_ptr(), flow.shape[1], flow.shape[2]
         if abs_sum is not None:
             d.abs_sum = abs_sum.data_ptr()
-        if kind == 6:
-            d.range_flag = _range_flag(dev).data_ptr()
-        with torch.cuda.device(dev), _apply_switch("head"):
-            _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
-    if _ConvFlops.enabled:
-        for (c0, c1), k in zip(slices, fam):
-            f = 2.0 * (c1 - c0) * 9 * Cin * H * W * B
-            _ConvFlops.add("dcn_head_" + _KINDS[k].family, f, f * _KINDS[k].exec_factor)
+        with _apply_switch("head"):
+            _launch_conv(d, dev, kind, "dcn_head_")
     return offset, mask
 
 
@@ -1136,43 +1141,35 @@ class BorderedNHWC:
 
 
 class _DcnWeightCache(_WeightCache):
-    @staticmethod
-    def _relayout_dcn(weight, dg, wt=None):
-        w = _dev_f32(weight.detach(), "weight")
-        Co, C, kh, kw = w.shape
-        L = _lib.lib()
-        nbytes = L.c2m_dcn_v2_relayout_bytes(C, Co, kh, kw, dg)
-        if nbytes == 0:
-            raise _lib.C2MError("dcn_v2_forward_nhwc: geometry is not on the channels-last path")
-        if wt is None:
-            wt = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
-        with torch.cuda.device(w.device):
-            _lib.check(L.c2m_dcn_v2_relayout_f32(_stream(), w.data_ptr(), C, Co, kh, kw, dg, wt.data_ptr()), "c2m_dcn_v2_relayout_f32")
-        return wt
+    # per DCNv2 kind: the C-ABI's size / re-layout entry points, what a geometry without that image is told
+    _IMAGES = {K_DCN: ("c2m_dcn_v2_relayout_bytes", "c2m_dcn_v2_relayout_f32", "geometry is not on the channels-last path"),
+               K_DCN16: ("c2m_dcn_v2_relayout_f16x2_bytes", "c2m_dcn_v2_relayout_f16x2",
+                         "geometry has no f16 x 2 kernel (needs >= 16 channels per (virtual) group)")}
 
-    @staticmethod
-    def _relayout_dcn16(weight, dg, wt=None):
+    @classmethod
+    def _relayout_dcn(cls, weight, dg, kind, wt=None):
+        size_fn, relayout_fn, why = cls._IMAGES[kind]
         w = _dev_f32(weight.detach(), "weight")
         Co, C, kh, kw = w.shape
         L = _lib.lib()
-        nbytes = L.c2m_dcn_v2_relayout_f16x2_bytes(C, Co, kh, kw, dg)
+        nbytes = getattr(L, size_fn)(C, Co, kh, kw, dg)
         if nbytes == 0:
-            raise _lib.C2MError("dcn_v2_forward_nhwc: geometry has no f16 x 2 kernel (needs >= 16 channels per (virtual) group)")
+            raise _lib.C2MError("dcn_v2_forward_nhwc: " + why)
         if wt is None:
             wt = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
         with torch.cuda.device(w.device):
-            _lib.check(L.c2m_dcn_v2_relayout_f16x2(_stream(), w.data_ptr(), C, Co, kh, kw, dg, wt.data_ptr()), "c2m_dcn_v2_relayout_f16x2")
+            _lib.check(getattr(L, relayout_fn)(_stream(), w.data_ptr(), C, Co, kh, kw, dg, wt.data_ptr()), relayout_fn)
         return wt
 
     def get(self, weight, dg, f16x2=False):
         key = (weight.data_ptr(), weight._version, tuple(weight.shape), dg, weight.device.index)
-        slot = (id(weight), None, "dcn16") if f16x2 else id(weight)
+        kind = K_DCN16 if f16x2 else K_DCN
+        slot = (id(weight), None, kind)
         hit = self._lookup(slot, key, weight)
         if hit is not None:
             return hit
-        fn = self._relayout_dcn16 if f16x2 else self._relayout_dcn
-        wt = fn(weight, dg)
-        self._store(slot, key, weight, wt, redo=lambda w, buf, dg=dg, fn=fn: fn(w, dg, buf))
+        wt = self._relayout_dcn(weight, dg, kind)
+        self._store(slot, key, weight, wt, redo=lambda w, buf, dg=dg, kind=kind: self._relayout_dcn(w, dg, kind, buf))
         return wt
 
 
@@ -1187,7 +1184,7 @@ def refresh_weight_caches(module_or_params=None, all_kinds=False):
     this once per forward: in-place writes through ``param.data`` do not bump the version counter the caches are keyed
     on, so without it such an update would keep computing with the old weights.  Returns the number of
     images rebuilt.  No host synchronisation."""
-    if _os.environ.get("C2M_WEIGHT_REFRESH", "1") == "0":   # measurement only: what the per-forward refresh costs
+    if os.environ.get("C2M_WEIGHT_REFRESH", "1") == "0":   # measurement only: what the per-forward refresh costs
         return 0
     ids = None
     if module_or_params is not None:
@@ -1195,7 +1192,7 @@ def refresh_weight_caches(module_or_params=None, all_kinds=False):
         ids = {id(p) for p in params}
     kinds = None
     if not all_kinds and not torch.is_grad_enabled():
-        kinds = {0, 1, 2, 4} if bf16_autocast() else ({0, 1, 2, 6} if _f16x2_auto() else {0, 1, 2, 3})
+        kinds = {*_MFMA32_KINDS, _split_kind(None)}
     return _wcache.refresh(ids, kinds) + _dcn_wcache.refresh(ids)
 
 
@@ -1266,22 +1263,20 @@ def dcn_v2_forward_nhwc(inp_bordered, weight, bias, offset, mask, deformable_gro
 def _bordered_empty(B, C, H, W, device, grouped8=False):
     """BorderedNHWC whose border is zero and whose interior is uninitialised (to be written by a conv epilogue).
     grouped8: also allocate the group-major twin (same border)."""
+    def zero_border(t):     # [..., H + 3, W + 3, channels]: row 0, rows H + 1 .., column 0, columns W + 1 ..
+        t[..., 0, :, :].zero_()
+        t[..., H + 1:, :, :].zero_()
+        t[..., 1:H + 1, 0, :].zero_()
+        t[..., 1:H + 1, W + 1:, :].zero_()
+        return t
+
     o = BorderedNHWC.__new__(BorderedNHWC)
     o.B, o.C, o.H, o.W = B, C, H, W
-    o.buf = torch.empty((B, H + 3, W + 3, C), dtype=torch.float32, device=device)
-    o.buf[:, 0].zero_()
-    o.buf[:, H + 1:].zero_()
-    o.buf[:, 1:H + 1, 0].zero_()
-    o.buf[:, 1:H + 1, W + 1:].zero_()
+    o.buf = zero_border(torch.empty((B, H + 3, W + 3, C), dtype=torch.float32, device=device))
     if grouped8:
         if C % 8 != 0:
             raise _lib.C2MError("a group-major twin needs C % 8 == 0")
-        g = torch.empty((B, C // 8, H + 3, W + 3, 8), dtype=torch.float32, device=device)
-        g[:, :, 0].zero_()
-        g[:, :, H + 1:].zero_()
-        g[:, :, 1:H + 1, 0].zero_()
-        g[:, :, 1:H + 1, W + 1:].zero_()
-        o.grouped8 = g
+        o.grouped8 = zero_border(torch.empty((B, C // 8, H + 3, W + 3, 8), dtype=torch.float32, device=device))
     return o
 
 

@@ -1459,7 +1459,7 @@ extern "C" int c2m_conv3x3_relayout_split_dgrad_f32(c2m_stream_t stream, const f
 }
 
 namespace {
-inline int conv_mw(int Cout) { return Cout <= 32 ? 32 : 64; }
+inline int conv_mw(int Cout) { return 32 * conv::cout_tiles(Cout); }
 inline long long relayout_elems(int Cin, int Cout) {
   const int MW = conv_mw(Cout), ncb = (Cout + MW - 1) / MW;
   return (long long)ncb * (Cin / conv::KCH) * 9 * MW * 32;
@@ -1592,9 +1592,8 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   // 32 x 8 pixel tiles for every width.  The kernel also instantiates as 64 x 4 (PX = 32); measured on the decoder's shapes
   // (B=16) that is 3-10 % slower -- its 66 x 6 halo re-reads 1.55x the tile from L2/HBM against 1.33x for 34 x 10, and the
   // halo traffic is what this kernel stalls on (64->64 @640x640: 3.17 ms vs 2.93 ms; without input DMA 2.76 ms).
-  const bool wino64 = false;
-  p.tiles_x = ceil_div(d->W, wino4 ? conv::wino4::TWX : wino ? (wino64 ? 64 : 32) : conv::TW);
-  p.tiles_y = ceil_div(d->H, wino4 ? conv::wino4::THY : wino && !wino64 ? 8 : conv::TH);
+  p.tiles_x = ceil_div(d->W, wino4 ? conv::wino4::TWX : wino ? 32 : conv::TW);
+  p.tiles_y = ceil_div(d->H, wino4 ? conv::wino4::THY : wino ? 8 : conv::TH);
   p.nchunks = d->Cin / kch;
   for (int s = 0; s < 2; ++s) {
     const int k = s < d->nsrc ? s : 0;
@@ -1647,66 +1646,28 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
     ProfileScope prof(C2M_KERNEL_CONV3X3_SPLIT, as_stream(stream));
     return conv::launch_split(as_stream(stream), p, d->algo == C2M_CONV_BF16 ? 1 : (d->algo == C2M_CONV_SPLIT_F16X2 ? 2 : 3));
   }
-  // tiles per workgroup: long streams amortise the set-up and the first DMA wait, but the launch is only as fast as its
-  // last round of 512 resident workgroups (2 per CU; the F(4,3) kernel: 256, 1 per CU): take the tpw <= 10 with the fewest
-  // "rounds x tiles" (ties: the longer stream), e.g. 51200 tiles -> 10 (10 full rounds), 12800 -> 5 (5 full rounds).
-  // C2M_CONV_TPW overrides.
-  static const int env_tpw = [] { const char* e = getenv("C2M_CONV_TPW"); return e ? atoi(e) : 0; }();
+  // 512 resident workgroups (2 per CU; the F(4,3) kernel: 256, 1 per CU), at most 10 tiles each
   const int ncb = ceil_div(d->Cout, MW);
-  const long long resident = wino4 ? 256 : 512;
-  long long tpw = 1, best = -1;
-  for (long long t = 1; t <= 10; ++t) {
-    const long long wgs = ((ntile + t - 1) / t) * ncb;
-    const long long cost = ((wgs + resident - 1) / resident) * t;
-    if (best < 0 || cost <= best) { best = cost; tpw = t; }
-  }
-  if (env_tpw > 0) tpw = env_tpw;
-  p.tpw = (int)tpw;
-  dim3 grid((unsigned)((ntile + tpw - 1) / tpw), ncb);
+  p.tpw = conv::tiles_per_workgroup(ntile, ncb, wino4 ? 256 : 512, 10);
+  dim3 grid((unsigned)((ntile + p.tpw - 1) / p.tpw), ncb);
   hipStream_t st = as_stream(stream);
   ProfileScope prof(C2M_KERNEL_CONV3X3, st);
-  const size_t ldsb = 2 * conv::IN_BYTES + 3 * (size_t)MW * 128 + 1024 + 256;   // halo x2, weight ring, DMA dummy, bias
-  int rc = C2M_OK;
-  auto go = [&](auto kern, unsigned long long& done) {
-    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ldsb, done)) != C2M_OK) return;
-    hipLaunchKernelGGL(kern, grid, dim3(256), ldsb, st, p);
-  };
-  static unsigned long long done[2][4] = {};
-  if (wino4) {
-    static unsigned long long done_w4 = 0;
-    const size_t lds4 = 2 * conv::wino4::IN_BYTES + conv::wino4::NRING * conv::wino4::WUNIT + 1024 + 256;
-    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv::conv3x3_wino4_kernel), lds4, done_w4)) == C2M_OK)
-      hipLaunchKernelGGL(conv::conv3x3_wino4_kernel, grid, dim3(256), lds4, st, p);
-  } else if (wino) {
-    static unsigned long long done_w[2][2] = {};
-    const size_t ldsw = 2 * conv::wino::IN_BYTES + conv::wino::NRING * conv::wino::WUNIT + 1024 + 256;
-    auto gow = [&](auto kern, unsigned long long& dn) {
-      if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ldsw, dn)) != C2M_OK) return;
-      hipLaunchKernelGGL(kern, grid, dim3(256), ldsw, st, p);
-    };
-    static unsigned long long done_pool = 0;
-    if (d->out_mode == 3) {
-      gow(&conv::conv3x3_wino_kernel<16, 3>, done_w[1][1]);
-    } else if (d->out_mode == 4) {
-      gow(&conv::conv3x3_wino_kernel<16, 4>, done_pool);
-    } else {
-      gow(&conv::conv3x3_wino_kernel<16, 0>, done_w[1][0]);
-    }
-  } else if (MW == 64) {
-    switch (d->out_mode) {
-      case 0: go(&conv::conv3x3_kernel<2, 0>, done[1][0]); break;
-      case 1: go(&conv::conv3x3_kernel<2, 1>, done[1][1]); break;
-      case 2: go(&conv::conv3x3_kernel<2, 2>, done[1][2]); break;
-      default: go(&conv::conv3x3_kernel<2, 3>, done[1][3]); break;
-    }
-  } else {
-    switch (d->out_mode) {
-      case 0: go(&conv::conv3x3_kernel<1, 0>, done[0][0]); break;
-      case 1: go(&conv::conv3x3_kernel<1, 1>, done[0][1]); break;
-      case 2: go(&conv::conv3x3_kernel<1, 2>, done[0][2]); break;
-      default: go(&conv::conv3x3_kernel<1, 3>, done[0][3]); break;
-    }
-  }
+  // dynamic LDS: halo x2, weight ring, DMA dummy, bias
+  const size_t lds = wino4  ? 2 * conv::wino4::IN_BYTES + conv::wino4::NRING * conv::wino4::WUNIT + 1024 + 256
+                     : wino ? 2 * conv::wino::IN_BYTES + conv::wino::NRING * conv::wino::WUNIT + 1024 + 256
+                            : 2 * conv::IN_BYTES + 3 * (size_t)MW * 128 + 1024 + 256;
+  struct Kernel { void (*fn)(conv::Params); unsigned long long lds_done; };   // entry point + its ensure_dynamic_lds flag
+  static Kernel wino4_kernel = {&conv::conv3x3_wino4_kernel, 0};
+  static Kernel wino_kernels[3] = {   // out_mode 0, 3 (DCN head), 4 (pooled)
+      {&conv::conv3x3_wino_kernel<16, 0>, 0}, {&conv::conv3x3_wino_kernel<16, 3>, 0}, {&conv::conv3x3_wino_kernel<16, 4>, 0}};
+  static Kernel direct_kernels[2][4] = {   // [MT - 1][out_mode 0 .. 3] (mode 4 was refused above)
+      {{&conv::conv3x3_kernel<1, 0>, 0}, {&conv::conv3x3_kernel<1, 1>, 0}, {&conv::conv3x3_kernel<1, 2>, 0}, {&conv::conv3x3_kernel<1, 3>, 0}},
+      {{&conv::conv3x3_kernel<2, 0>, 0}, {&conv::conv3x3_kernel<2, 1>, 0}, {&conv::conv3x3_kernel<2, 2>, 0}, {&conv::conv3x3_kernel<2, 3>, 0}}};
+  Kernel& k = wino4  ? wino4_kernel
+              : wino ? wino_kernels[d->out_mode == 3 ? 1 : d->out_mode == 4 ? 2 : 0]
+                     : direct_kernels[MW / 32 - 1][d->out_mode];
+  const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k.fn), lds, k.lds_done);
   if (rc != C2M_OK) return rc;
+  hipLaunchKernelGGL(k.fn, grid, dim3(256), lds, st, p);
   return check_launch();
 }

@@ -1,6 +1,8 @@
 // conv3x3_shared.h -- declarations shared by the 3x3 convolution kernels (conv3x3.hip: fp32-MFMA direct / Winograd kernels;
 // conv3x3_split.hip: the split-bf16 kernels): launch parameters, buffer-descriptor helpers, the DCN offset/mask head stores.
 #pragma once
+#include <stdlib.h>
+
 #include "c2m_common.h"
 
 namespace c2m {
@@ -43,6 +45,26 @@ struct Params {
   int io_flags;          // bf16 flavour: C2M_IO_* (element types of src[0] / out / res1 / res2)
   int* range_flag;       // f16 x 2 flavour: set to 1 if an input activation lies outside the flavour's domain (|x| >= 65520)
 };
+
+// ---- launch rules of the host code (conv3x3.hip: direct / Winograd kernels, conv3x3_split.hip: split kernels) ----
+// Output-channel tile of the direct and the split kernels: one 32-row MFMA tile for Cout <= 32, else two; a workgroup computes
+// MW = 32 * MT output channels (weight images are laid out for that MT: the re-layouts use the same rule).
+inline int cout_tiles(int Cout) { return Cout <= 32 ? 1 : 2; }
+
+// Tiles per workgroup: long streams amortise the set-up and the first DMA wait, but the launch is only as fast as its last
+// round of `resident` workgroups: take the tpw <= tmax with the fewest "rounds x tiles" (ties: the longer stream), e.g. at
+// 512 resident, tmax 10: 51200 tiles -> 10 (10 full rounds), 12800 -> 5 (5 full rounds).  $C2M_CONV_TPW overrides.
+inline int tiles_per_workgroup(long long ntile, int ncb, long long resident, int tmax) {
+  static const int env_tpw = [] { const char* e = getenv("C2M_CONV_TPW"); return e ? atoi(e) : 0; }();
+  if (env_tpw > 0) return env_tpw;
+  long long tpw = 1, best = -1;
+  for (long long t = 1; t <= tmax; ++t) {
+    const long long wgs = ((ntile + t - 1) / t) * ncb;
+    const long long cost = ((wgs + resident - 1) / resident) * t;
+    if (best < 0 || cost <= best) { best = cost; tpw = t; }
+  }
+  return (int)tpw;
+}
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {

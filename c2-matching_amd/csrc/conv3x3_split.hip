@@ -1030,7 +1030,7 @@ namespace conv {
 // np = flavour: 3 bf16 x 3, 1 bf16, 2 f16 x 2 (image + 256-byte tail holding 1/S)
 static size_t split_image_bytes(int Cin, int Cout, int np) {
   if (Cin <= 0 || Cout <= 0 || Cin % split::KC != 0 || (np != 1 && np != 2 && np != 3)) return 0;
-  const int MT = Cout <= 32 ? 1 : 2, ncb = (Cout + 32 * MT - 1) / (32 * MT);
+  const int MT = cout_tiles(Cout), ncb = (Cout + 32 * MT - 1) / (32 * MT);
   return (size_t)ncb * (Cin / split::KC) * 3 * 3 * split::npw_of(np) * MT * 1024;
 }
 
@@ -1050,7 +1050,7 @@ int split_relayout(hipStream_t st, const float* weight, int Cin, int Cout, int n
                        reinterpret_cast<unsigned*>(reinterpret_cast<char*>(wr) + bytes));
   }
   hipLaunchKernelGGL(split::conv3x3_relayout_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, weight, Cin,
-                     Cout, np, Cout <= 32 ? 1 : 2, total, reinterpret_cast<unsigned short*>(wr), dgrad);
+                     Cout, np, cout_tiles(Cout), total, reinterpret_cast<unsigned short*>(wr), dgrad);
   return check_launch();
 }
 
@@ -1063,42 +1063,35 @@ int split_relayout_multi(hipStream_t st, const long long* jobs, int njobs, long 
 
 thread_local int g_head_stores = -1;   // c2m_conv3x3_set_head_stores
 
-template <int NP, int MT>
-static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid) {
-  constexpr size_t ldsb = (size_t)((NP != 3 ? 2 : 1) * split::npx_of(NP) * 2 * split::HALFB) + (NP != 3 ? 3 : 2) * (size_t)(3 * split::npw_of(NP) * MT * 1024) + 1024 +
-                          256;   // planes (x2 when pipelined), weight ring (3 / 2 slots), dummy, bias
-  static unsigned long long done[5] = {};
-  int rc = C2M_OK;
-  auto go = [&](auto kern, unsigned long long& dn) {
-    if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), ldsb, dn)) == C2M_OK)
-      hipLaunchKernelGGL(kern, grid, dim3(256), ldsb, st, p);
-  };
+// One flavour's kernels: [MT - 1][MODE], MODE = Params::out_mode 0 .. 4, 5 = the DCN head (3) with 16-byte quad stores; each
+// entry point with its ensure_dynamic_lds flag.
+template <int NP>
+static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid, int MT) {
+  using split::conv3x3_split_kernel;
+  struct Kernel { void (*fn)(Params); unsigned long long lds_done; };
+  static Kernel kernels[2][6] = {
+      {{&conv3x3_split_kernel<NP, 1, 0>, 0}, {&conv3x3_split_kernel<NP, 1, 1>, 0}, {&conv3x3_split_kernel<NP, 1, 2>, 0},
+       {&conv3x3_split_kernel<NP, 1, 3>, 0}, {&conv3x3_split_kernel<NP, 1, 4>, 0}, {&conv3x3_split_kernel<NP, 1, 5>, 0}},
+      {{&conv3x3_split_kernel<NP, 2, 0>, 0}, {&conv3x3_split_kernel<NP, 2, 1>, 0}, {&conv3x3_split_kernel<NP, 2, 2>, 0},
+       {&conv3x3_split_kernel<NP, 2, 3>, 0}, {&conv3x3_split_kernel<NP, 2, 4>, 0}, {&conv3x3_split_kernel<NP, 2, 5>, 0}}};
+  // planes (x2 when pipelined), weight ring (3 / 2 slots), dummy, bias
+  size_t ldsb = (size_t)((NP != 3 ? 2 : 1) * split::npx_of(NP) * 2 * split::HALFB) + (NP != 3 ? 3 : 2) * (size_t)(3 * split::npw_of(NP) * MT * 1024) + 1024 + 256;
+  int mode = p.out_mode;
+  if (mode == 3) {
+    static const int env_quad = [] { const char* e = getenv("C2M_HEAD_QUAD"); return e ? atoi(e) : 1; }();
+    const int head_quad = g_head_stores >= 0 ? g_head_stores : env_quad;
+    if (head_quad != 0 && p.W % 4 == 0) mode = 5;
+  }
+  Kernel* k = &kernels[MT - 1][mode];
   if constexpr (NP == 1) {
     if (p.io_flags & C2M_IO_SRC_BF16) {   // bf16 source: three 12 KiB plane buffers filled by LDS-DMA
-      constexpr size_t lds16 = (size_t)3 * 12 * 1024 + 3 * (size_t)(3 * MT * 1024) + 1024 + 256;
-      static unsigned long long done16 = 0;
-      auto go16 = [&](auto kern, unsigned long long& dn) {
-        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds16, dn)) == C2M_OK)
-          hipLaunchKernelGGL(kern, grid, dim3(256), lds16, st, p);
-      };
-      go16(&split::conv3x3_split_kernel<1, MT, 0, true>, done16);
-      return rc;
+      static Kernel src16[2] = {{&conv3x3_split_kernel<1, 1, 0, true>, 0}, {&conv3x3_split_kernel<1, 2, 0, true>, 0}};
+      k = &src16[MT - 1];
+      ldsb = (size_t)3 * 12 * 1024 + 3 * (size_t)(3 * MT * 1024) + 1024 + 256;
     }
   }
-  switch (p.out_mode) {
-    case 0: go(&split::conv3x3_split_kernel<NP, MT, 0>, done[0]); break;
-    case 1: go(&split::conv3x3_split_kernel<NP, MT, 1>, done[1]); break;
-    case 2: go(&split::conv3x3_split_kernel<NP, MT, 2>, done[2]); break;
-    case 3: {
-      static const int env_quad = [] { const char* e = getenv("C2M_HEAD_QUAD"); return e ? atoi(e) : 1; }();
-      const int head_quad = g_head_stores >= 0 ? g_head_stores : env_quad;
-      static unsigned long long done5 = 0;
-      if (head_quad != 0 && p.W % 4 == 0) go(&split::conv3x3_split_kernel<NP, MT, 5>, done5);
-      else go(&split::conv3x3_split_kernel<NP, MT, 3>, done[3]);
-      break;
-    }
-    default: go(&split::conv3x3_split_kernel<NP, MT, 4>, done[4]); break;
-  }
+  const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(k->fn), ldsb, k->lds_done);
+  if (rc == C2M_OK) hipLaunchKernelGGL(k->fn, grid, dim3(256), ldsb, st, p);
   return rc;
 }
 
@@ -1107,25 +1100,12 @@ int launch_split(hipStream_t st, Params p, int np) {
   p.tiles_x = ceil_div(p.W, split::TWX);
   p.tiles_y = ceil_div(p.H, split::THY);
   p.nchunks = p.Cin / split::KC;
-  const int MT = p.Cout <= 32 ? 1 : 2, MW = 32 * MT;
-  const int ncb = ceil_div(p.Cout, MW);
+  const int MT = cout_tiles(p.Cout), ncb = ceil_div(p.Cout, 32 * MT);
   const long long ntile = (long long)p.tiles_x * p.tiles_y * p.B;
   if (ntile > 0x7fffffffLL) return C2M_ERR_INVALID_ARG;
-  static const int env_tpw = [] { const char* e = getenv("C2M_CONV_TPW"); return e ? atoi(e) : 0; }();
-  const long long resident = 512;   // two workgroups per CU (75 KiB of LDS, <= 256 registers each)
-  long long tpw = 1, best = -1;
-  for (long long t = 1; t <= 16; ++t) {
-    const long long wgs = ((ntile + t - 1) / t) * ncb;
-    const long long cost = ((wgs + resident - 1) / resident) * t;
-    if (best < 0 || cost <= best) { best = cost; tpw = t; }
-  }
-  if (env_tpw > 0) tpw = env_tpw;
-  p.tpw = (int)tpw;
-  dim3 grid((unsigned)((ntile + tpw - 1) / tpw), ncb);
-  int rc;
-  if (np == 3) rc = MT == 2 ? launch_split_mode<3, 2>(st, p, grid) : launch_split_mode<3, 1>(st, p, grid);
-  else if (np == 2) rc = MT == 2 ? launch_split_mode<2, 2>(st, p, grid) : launch_split_mode<2, 1>(st, p, grid);
-  else rc = MT == 2 ? launch_split_mode<1, 2>(st, p, grid) : launch_split_mode<1, 1>(st, p, grid);
+  p.tpw = tiles_per_workgroup(ntile, ncb, 512, 16);   // two workgroups per CU (75 KiB of LDS, <= 256 registers each)
+  dim3 grid((unsigned)((ntile + p.tpw - 1) / p.tpw), ncb);
+  const int rc = np == 3 ? launch_split_mode<3>(st, p, grid, MT) : np == 2 ? launch_split_mode<2>(st, p, grid, MT) : launch_split_mode<1>(st, p, grid, MT);
   if (rc != C2M_OK) return rc;
   return check_launch();
 }
