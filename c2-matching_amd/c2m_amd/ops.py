@@ -270,6 +270,12 @@ def _dcn_geom(inp, weight, stride, padding, dilation):
     return (B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw), Ho, Wo
 
 
+def _check_offset_mask(offset, mask, B, dg, taps, Ho, Wo, names):
+    """The planar offset / mask pair of a DCNv2 call; `names`: how the caller's message spells taps, Ho and Wo."""
+    if tuple(offset.shape) != (B, 2 * dg * taps, Ho, Wo) or tuple(mask.shape) != (B, dg * taps, Ho, Wo):
+        raise _lib.C2MError("offset/mask shape does not match [B, 2*dg*{0}, {1}, {2}] / [B, dg*{0}, {1}, {2}]".format(*names))
+
+
 def dcn_v2_forward(inp, weight, bias, offset, mask, stride=1, padding=1, dilation=1, deformable_groups=1,
                    bf16_mma=False):
     """bf16_mma=True: the implicit GEMM runs on bf16 MFMA with fp32 accumulation (weights and blended samples rounded to
@@ -279,8 +285,7 @@ def dcn_v2_forward(inp, weight, bias, offset, mask, stride=1, padding=1, dilatio
     g, Ho, Wo = _dcn_geom(inp, weight, stride, padding, dilation)
     B, C, H, W, Co, kh, kw = g[:7]
     dg = int(deformable_groups)
-    if tuple(offset.shape) != (B, 2 * dg * kh * kw, Ho, Wo) or tuple(mask.shape) != (B, dg * kh * kw, Ho, Wo):
-        raise _lib.C2MError("offset/mask shape does not match [B, 2*dg*kh*kw, Ho, Wo] / [B, dg*kh*kw, Ho, Wo]")
+    _check_offset_mask(offset, mask, B, dg, kh * kw, Ho, Wo, ("kh*kw", "Ho", "Wo"))
     L = _lib.lib()
     with torch.cuda.device(inp.device):
         nbytes = L.c2m_dcn_v2_forward_workspace_bytes(B, C, H, W, Co, kh, kw, dg)
@@ -1222,8 +1227,7 @@ def dcn_v2_forward_nhwc(inp_bordered, weight, bias, offset, mask, deformable_gro
     Co = weight.shape[0]
     dg = int(deformable_groups)
     offset, mask, bias = _dev_f32(offset, "offset"), _dev_f32(mask, "mask"), _dev_f32(bias.detach(), "bias")
-    if tuple(offset.shape) != (B, 2 * dg * 9, H, W) or tuple(mask.shape) != (B, dg * 9, H, W):
-        raise _lib.C2MError("offset/mask shape does not match [B, 2*dg*9, H, W] / [B, dg*9, H, W]")
+    _check_offset_mask(offset, mask, B, dg, 9, H, W, ("9", "H", "W"))
     if algo is None:
         f16 = _DCN_F16X2 and _SPLIT != "0" and _f16x2_auto() and dcn_f16x2_ok(weight, dg)
     elif algo in ("fp32", "f16x2"):
@@ -1241,19 +1245,12 @@ def dcn_v2_forward_nhwc(inp_bordered, weight, bias, offset, mask, deformable_gro
         pitches = (0, 0, 0, 0)
     grouped = inp_bordered.grouped8 is not None and C == 8 * dg
     src = inp_bordered.grouped8 if grouped else inp_bordered.buf
+    fn = "c2m_dcn_v2_forward_nhwc_f16x2" if f16 else "c2m_dcn_v2_forward_nhwc_f32"
     with torch.cuda.device(dev):
-        if f16:
-            _lib.check(_lib.lib().c2m_dcn_v2_forward_nhwc_f16x2(_stream(), src.data_ptr(), wt.data_ptr(), bias.data_ptr(),
-                                                               offset.data_ptr(), mask.data_ptr(), B, C, H, W, Co, 3, 3, 1, 1, 1,
-                                                               1, 1, 1, dg, out.data_ptr(), *pitches, int(act), float(slope),
-                                                               int(grouped), _range_flag(dev).data_ptr()),
-                       "c2m_dcn_v2_forward_nhwc_f16x2")
-        else:
-            _lib.check(_lib.lib().c2m_dcn_v2_forward_nhwc_f32(_stream(), src.data_ptr(), wt.data_ptr(), bias.data_ptr(),
-                                                             offset.data_ptr(), mask.data_ptr(), B, C, H, W, Co, 3, 3, 1, 1, 1, 1,
-                                                             1, 1, dg, out.data_ptr(), *pitches, int(act), float(slope),
-                                                             int(grouped)),
-                       "c2m_dcn_v2_forward_nhwc_f32")
+        tail = (_range_flag(dev).data_ptr(),) if f16 else ()   # the f16 x 2 entry point takes the range flag last
+        _lib.check(getattr(_lib.lib(), fn)(_stream(), src.data_ptr(), wt.data_ptr(), bias.data_ptr(), offset.data_ptr(),
+                                           mask.data_ptr(), B, C, H, W, Co, 3, 3, 1, 1, 1, 1, 1, 1, dg, out.data_ptr(), *pitches,
+                                           int(act), float(slope), int(grouped), *tail), fn)
     return out
 
 

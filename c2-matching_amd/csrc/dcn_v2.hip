@@ -29,6 +29,8 @@
 // K orders: NCHW kernels k = (g * T + tap) * CPG + c_in_group (T = kh*kw, CPG = C/dg); channels-last forward
 // (tap, group, kk) with kk = 2t + hi <-> channel t + hi * CPG/2; offset/mask kernel: see weight_relayout_kernel.
 // Weights are re-laid out once per call (Wt[k][Co] forward, Wb[o][k] backward, Wh[k/8][Co][8] bf16).
+#include <type_traits>
+
 #include "c2m_common.h"
 
 namespace c2m {
@@ -1374,84 +1376,141 @@ inline int copad_fwd(int Co) {
 }
 inline int copad2(int Co) { return Co <= 64 ? 64 : Co <= 128 ? 128 : Co <= 256 ? 256 : -1; }
 
-template <int MT, int NT, int CPG, int GC, bool SPLITG, bool BF16, bool F16X2>
-int launch_fwd_nhwc(hipStream_t st, const float* inl, const float* wt, const float* bias, const float* off,
-                    const float* msk, const Geom& g, float* out) {
-  const int HWo = g.Ho * g.Wo;
-  const size_t lds = (BF16 ? 2 : 4) * 2 * (size_t)GC * CPG * MT * 32;
-  static unsigned long long lds_set = 0;
-  if (lds > 48 * 1024)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&dcn::dcn_fwd_nhwc_kernel<MT, NT, CPG, GC, SPLITG, BF16, F16X2>), lds, lds_set))
-      return rc;
-  dim3 grid(ceil_div(HWo, 4 * NT * 32), g.B, g.CoPad / (MT * 32));
-  hipLaunchKernelGGL((dcn::dcn_fwd_nhwc_kernel<MT, NT, CPG, GC, SPLITG, BF16, F16X2>), grid, dim3(256), lds, st, inl, wt, bias, off, msk, g, out);
-  return C2M_OK;
-}
-
-// groups per weight chunk: the largest power of two dividing dg with chunk <= 32 KiB (and >= 4 KiB so that every wave's
-// quarter is a whole number of 1 KiB DMA pieces)
-template <int MT, int NT, int CPG, bool SPLITG, bool BF16, bool F16X2>
-int pick_gc_fwd_nhwc(hipStream_t st, const float* inl, const float* wt, const float* bias, const float* off,
-                     const float* msk, const Geom& g, float* out) {
-  constexpr int ROWB = CPG * MT * 32 * (BF16 ? 2 : 4);  // bytes of one group's weight rows
-  // groups that fit a 32 KiB chunk (64 KiB for the one-wave-per-SIMD MT = 8 variant)
-  constexpr int FIT = ((MT == 8 ? 64 : 32) * 1024) / ROWB;
-  if constexpr (FIT >= 8) {
-    if (g.dg % 8 == 0) return launch_fwd_nhwc<MT, NT, CPG, 8, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);
-  }
-  if constexpr (FIT >= 4) {
-    if (g.dg % 4 == 0) return launch_fwd_nhwc<MT, NT, CPG, 4, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);
-  }
-  static_assert(FIT >= 2, "two groups' weight rows must fit one chunk");
-  return launch_fwd_nhwc<MT, NT, CPG, 2, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);   // use_nhwc() guarantees an even dg
-}
-
-template <int CPG, bool SPLITG, bool BF16, bool F16X2 = false>
-int dispatch_fwd_nhwc(hipStream_t st, int mt, const float* inl, const float* wt, const float* bias, const float* off,
-                      const float* msk, const Geom& g, float* out) {
-  // Register budget (256 VGPRs at 2 waves/SIMD): MT*NT*16 accumulators + two generations of gathered corners
-  // (NT*4*CPG/2 values each) + column values.  Co > 128 is split over grid.z (each workgroup re-gathers: cheap next to
-  // the MFMA work of >= 128 output channels).
-  // one pixel tile per wave everywhere: for 8-channel groups that means ~110 VGPRs = 4 waves/SIMD, which hides the gather
-  // latency better than a second pixel tile amortises the LDS weight reads (large layer, B=16: 10.4 -> 8.4 ms)
-  constexpr int NT2 = 1;
-  switch (mt) {
-    case 1: return pick_gc_fwd_nhwc<1, NT2, CPG, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);
-    case 2: return pick_gc_fwd_nhwc<2, NT2, CPG, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);
-    case 8:
-      // bf16: the kernel is gather/blend bound, so all 256 output channels share one gathered column (one wave per SIMD,
-      // 128 accumulator registers) instead of splitting Co over grid.z and gathering twice.  (fp32: measured, no gain.)
-      if constexpr (BF16 && CPG == 32) return pick_gc_fwd_nhwc<8, 1, CPG, SPLITG, BF16, false>(st, inl, wt, bias, off, msk, g, out);
-      // f16 x 2 likewise: gather bound (small layer, B=16: 4.27 -> 2.70 ms)
-      if constexpr (F16X2 && CPG == 32) return pick_gc_fwd_nhwc<8, 1, CPG, SPLITG, false, true>(st, inl, wt, bias, off, msk, g, out);
-      [[fallthrough]];
-    default: return pick_gc_fwd_nhwc<4, 1, CPG, SPLITG, BF16, F16X2>(st, inl, wt, bias, off, msk, g, out);
-  }
+// bytes of the zero-bordered channels-last (or group-major) copy of a [B][C][H][W] input, as a workspace piece
+inline size_t bordered_copy_bytes(int B, int C, int H, int W) {
+  return align256(sizeof(float) * (size_t)B * C * (H + 3) * (W + 3));
 }
 
 // channels-last fast path: 8/16/32 channels per deformable group and an even number of groups (its step pairs and weight
 // chunks cover two groups at a time); everything else takes the NCHW kernel
-// (and samples whose staged copy or offset planes reach 2 GiB: the kernel addresses them with 32-bit buffer offsets)
+// (and samples whose staged copy or offset planes reach 2 GiB: the kernel addresses them with 32-bit buffer offsets).
+// The copy's limit is not bordered_copy_bytes(1, ...): rounded up to 256, a sample within 256 bytes of 2 GiB would change sides.
 inline bool use_nhwc(const Geom& g) {
   const unsigned long long lim = 1ull << 31;
   const unsigned long long copy = 4ull * g.C * (g.H + 3) * (g.W + 3), offs = 4ull * g.dg * 2 * g.T * g.Ho * g.Wo;
   return (g.CPG == 8 || g.CPG == 16 || g.CPG == 32) && g.dg % 2 == 0 && copy < lim && offs < lim;
 }
 
+// The geometry a channels-last kernel and its weight image see, for a `g` with use_nhwc(g).  8-channel groups are processed
+// as virtual groups of two (see SPLITG): the kernel and the weight re-layout see the virtual grouping, which leaves the K
+// order a plain (tap, group, kk) order over real channels; dg % 4 == 0 because the virtual grouping must keep an even group
+// count.  (Measured, B=16: large layer 16.4 -> 13.7 ms on random flows, 7.6 -> 7.1 ms on coherent ones; 16-channel groups
+// lose 2-10 %, so they stay.)  The rule reads C and dg only, so the image made from the probe geometry (relayout_geom) is
+// the one the forward of any map size multiplies with: dcn_forward asks use_nhwc of the real geometry, the re-layout entry
+// points of the probe, and a forward that is handed an image (FwdExt::wt) on a geometry off the fast path is refused.
+inline Geom kernel_geom(const Geom& g) {
+  Geom gk = g;
+  if (g.CPG == 8 && g.dg % 4 == 0) { gk.CPG = 2 * g.CPG; gk.dg = g.dg / 2; }
+  return gk;
+}
+
+// Geometry of a weight re-layout, which has no map: does a weight of this shape have a channels-last image?  Probed on an
+// 8 x 8 map (use_nhwc's size limits cannot trip there); fills g.CoPad.
+int relayout_geom(Geom& g, int C, int Co, int kh, int kw, int dg) {
+  const int rc = make_geom(g, 1, C, 8, 8, Co, kh, kw, 1, 1, kh / 2, kw / 2, 1, 1, dg);
+  if (rc != C2M_OK) return rc;
+  if (!use_nhwc(g)) return C2M_ERR_UNSUPPORTED;
+  g.CoPad = copad_fwd(Co);
+  return C2M_OK;
+}
+
+// f(std::integral_constant<int, V>()) for the V of the list that equals v: turns a run-time choice into a template argument
+template <int... Vs, typename F>
+inline bool with_constant(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
+}
+
+// Launch a 256-thread kernel with `lds` bytes of dynamic LDS; above the 48 KiB a kernel gets by default its limit is raised
+// first (once per device: `lds_set` is this instantiation's, that is this kernel's, flag).
+template <auto Kernel, typename... Args>
+int launch_dynamic_lds(dim3 grid, size_t lds, hipStream_t st, Args... args) {
+  static unsigned long long lds_set = 0;
+  if (lds > 48 * 1024)
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds, lds_set)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, args...);
+  return C2M_OK;
+}
+
+// what a forward launch carries down to its kernel; `g` is the geometry the kernel sees (kernel_geom)
+struct FwdArgs {
+  hipStream_t st;
+  const float *in, *wt, *bias, *off, *msk;
+  const Geom& g;
+  float* out;
+};
+
+enum { FP32, BF16, F16X2 };   // arithmetic of the channels-last forward's GEMM
+
+// The dcn_fwd_nhwc_kernel instantiations.  The reduced arithmetics need >= 16 channels per (virtual) group.  MT = 8:
+// bf16: the kernel is gather/blend bound, so all 256 output channels share one gathered column (one wave per SIMD, 128
+// accumulator registers) instead of splitting Co over grid.z and gathering twice (fp32: measured, no gain); f16 x 2
+// likewise: gather bound (small layer, B=16: 4.27 -> 2.70 ms).
+constexpr bool fwd_nhwc_has(int arith, int cpg, int mt) {
+  return (arith == FP32 || cpg >= 16) && (mt < 8 || (arith != FP32 && cpg == 32));
+}
+
+// Register budget (256 VGPRs at 2 waves/SIMD): MT*NT*16 accumulators + two generations of gathered corners
+// (NT*4*CPG/2 values each) + column values.  Co > 128 is split over grid.z (each workgroup re-gathers: cheap next to
+// the MFMA work of >= 128 output channels).
+// one pixel tile per wave everywhere: for 8-channel groups that means ~110 VGPRs = 4 waves/SIMD, which hides the gather
+// latency better than a second pixel tile amortises the LDS weight reads (large layer, B=16: 10.4 -> 8.4 ms)
+template <int ARITH, int CPG, bool SPLITG, int MT, int GC>
+int launch_fwd_nhwc(const FwdArgs& a) {
+  constexpr int NT = 1;
+  const Geom& g = a.g;
+  const size_t lds = (ARITH == BF16 ? 2 : 4) * 2 * (size_t)GC * CPG * MT * 32;
+  dim3 grid(ceil_div(g.Ho * g.Wo, 4 * NT * 32), g.B, g.CoPad / (MT * 32));
+  return launch_dynamic_lds<&dcn::dcn_fwd_nhwc_kernel<MT, NT, CPG, GC, SPLITG, ARITH == BF16, ARITH == F16X2>>(
+      grid, lds, a.st, a.in, a.wt, a.bias, a.off, a.msk, g, a.out);
+}
+
+// The one selection of a channels-last forward kernel: arithmetic x channels per (virtual) group x m-tiles per wave, then
+// the groups per weight chunk: the largest power of two dividing dg with chunk <= 32 KiB (and >= 4 KiB so that every
+// wave's quarter is a whole number of 1 KiB DMA pieces).  `split`: a.g is a virtual grouping (kernel_geom).
+int select_fwd_nhwc(const FwdArgs& a, int arith, bool split) {
+  const Geom& g = a.g;
+  const int mt = fwd_nhwc_has(arith, g.CPG, fwd_mt(g.Co)) ? fwd_mt(g.Co) : 4;
+  int rc = C2M_ERR_UNSUPPORTED;
+  with_constant<FP32, BF16, F16X2>(arith, [&](auto arith_c) {
+    with_constant<8, 16, 32>(g.CPG, [&](auto cpg_c) {
+      with_constant<1, 2, 4, 8>(mt, [&](auto mt_c) {
+        constexpr int ARITH = decltype(arith_c)::value, CPG = decltype(cpg_c)::value, MT = decltype(mt_c)::value;
+        if constexpr (fwd_nhwc_has(ARITH, CPG, MT)) {
+          constexpr int ROWB = CPG * MT * 32 * (ARITH == BF16 ? 2 : 4);  // bytes of one group's weight rows
+          // groups that fit a 32 KiB chunk (64 KiB for the one-wave-per-SIMD MT = 8 variant)
+          constexpr int FIT = ((MT == 8 ? 64 : 32) * 1024) / ROWB;
+          static_assert(FIT >= 2, "two groups' weight rows must fit one chunk");
+          const int gc = (FIT >= 8 && g.dg % 8 == 0) ? 8 : (FIT >= 4 && g.dg % 4 == 0) ? 4 : 2;   // use_nhwc(): dg is even
+          with_constant<2, 4, 8>(gc, [&](auto gc_c) {
+            constexpr int GC = decltype(gc_c)::value;
+            if constexpr (GC <= FIT) {
+              if constexpr (CPG == 16) {   // the only virtual grouping: pairs of 8-channel groups
+                if (split) { rc = launch_fwd_nhwc<ARITH, CPG, true, MT, GC>(a); return; }
+              }
+              rc = launch_fwd_nhwc<ARITH, CPG, false, MT, GC>(a);
+            }
+          });
+        }
+      });
+    });
+  });
+  return rc;
+}
+
 template <int MT, int NT>
-void launch_fwd(hipStream_t st, const float* in, const float* wt, const float* bias, const float* off, const float* msk,
-                const Geom& g, float* out) {
-  const int HWo = g.Ho * g.Wo;
-  dim3 grid(ceil_div(HWo, 4 * NT * 32), g.B, g.CoPad / (MT * 32));
-  hipLaunchKernelGGL((dcn::dcn_fwd_mfma_kernel<MT, NT>), grid, dim3(256), 0, st, in, wt, bias, off, msk, g, out);
+void launch_fwd(const FwdArgs& a) {
+  const Geom& g = a.g;
+  dim3 grid(ceil_div(g.Ho * g.Wo, 4 * NT * 32), g.B, g.CoPad / (MT * 32));
+  hipLaunchKernelGGL((dcn::dcn_fwd_mfma_kernel<MT, NT>), grid, dim3(256), 0, a.st, a.in, a.wt, a.bias, a.off, a.msk, g, a.out);
 }
 }  // namespace
 
+// (the workspace is sized for a pad of (kh, kw): its Ho x Wo only enter through use_nhwc's limit on the offset planes)
 extern "C" size_t c2m_dcn_v2_forward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int dg) {
   Geom g;
   if (make_geom(g, B, C, H, W, Co, kh, kw, 1, 1, kh, kw, 1, 1, dg) != C2M_OK) return 0;
   size_t n = align256(sizeof(float) * (size_t)g.KtotPad * copad_fwd(Co));
-  if (use_nhwc(g)) n += align256(sizeof(float) * (size_t)B * C * (H + 3) * (W + 3));  // zero-bordered channels-last copy
+  if (use_nhwc(g)) n += bordered_copy_bytes(B, C, H, W);
   return n;
 }
 
@@ -1502,26 +1561,22 @@ int dcn_forward(c2m_stream_t stream, const float* input, const float* weight, co
   g.out_img_pitch = ext.out_img_pitch; g.act = ext.act; g.slope = ext.slope;
   g.range_flag = ext.range_flag;
   const size_t wbytes = ext.wt ? 0 : align256(sizeof(float) * (size_t)g.KtotPad * g.CoPad);
-  const size_t need = wbytes + ((nhwc && !ext.inl) ? align256(sizeof(float) * (size_t)B * C * (H + 3) * (W + 3)) : 0);
+  const size_t need = wbytes + ((nhwc && !ext.inl) ? bordered_copy_bytes(B, C, H, W) : 0);
   if (need > 0 && (!workspace || workspace_bytes < need)) return C2M_ERR_WORKSPACE;
+  // 8-channel groups gather from a group-major copy (see Geom::in_grouped); a caller-provided copy says which it is
+  if (ext.in_grouped && !(ext.inl && nhwc && g.CPG == 8)) return C2M_ERR_UNSUPPORTED;
+  g.in_grouped = (ext.inl ? ext.in_grouped != 0 : (nhwc && g.CPG == 8)) ? 1 : 0;
+  const Geom gk = nhwc ? kernel_geom(g) : g;
+  const bool split = gk.dg != g.dg;
+  // bf16 MFMA variant: channels-last geometries whose half-run is a multiple of 8 channels; anything else computes in fp32
+  const bool bf16 = want_bf16 && nhwc && gk.CPG >= 16;
+  if (ext.f16x2 && (!ext.wt || !nhwc || gk.CPG < 16)) return C2M_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* wt = ext.wt ? const_cast<float*>(ext.wt) : static_cast<float*>(workspace);
   float* inl = ext.inl ? const_cast<float*>(ext.inl) : reinterpret_cast<float*>(static_cast<char*>(workspace) + wbytes);
-  // 8-channel groups are processed as virtual groups of two (see SPLITG): the kernel and the weight re-layout see the
-  // virtual grouping, which leaves the K order a plain (tap, group, kk) order over real channels.  (Measured, B=16: large
-  // layer 16.4 -> 13.7 ms on random flows, 7.6 -> 7.1 ms on coherent ones; 16-channel groups lose 2-10 %, so they stay.)
-  const bool split = nhwc && g.CPG == 8 && g.dg % 4 == 0;   // the virtual grouping must keep an even group count
-  Geom gk = g;
-  if (split) { gk.CPG = 2 * g.CPG; gk.dg = g.dg / 2; }
-  // bf16 MFMA variant: channels-last geometries whose half-run is a multiple of 8 channels; anything else computes in fp32
-  const bool bf16 = want_bf16 && nhwc && gk.CPG >= 16;
-  // 8-channel groups gather from a group-major copy (see Geom::in_grouped); a caller-provided copy says which it is
-  if (ext.in_grouped && !(ext.inl && nhwc && g.CPG == 8)) return C2M_ERR_UNSUPPORTED;
-  const bool grouped = ext.inl ? ext.in_grouped != 0 : (nhwc && g.CPG == 8);
-  g.in_grouped = gk.in_grouped = grouped ? 1 : 0;
   if (nhwc && !ext.inl) {
-    if (bf16) launch_nhwc_copy(st, input, B, C, H, W, reinterpret_cast<__bf16*>(inl), grouped);
-    else launch_nhwc_copy(st, input, B, C, H, W, inl, grouped);
+    if (bf16) launch_nhwc_copy(st, input, B, C, H, W, reinterpret_cast<__bf16*>(inl), g.in_grouped != 0);
+    else launch_nhwc_copy(st, input, B, C, H, W, inl, g.in_grouped != 0);
   }
   if (!ext.wt) {
     if (bf16)
@@ -1532,38 +1587,32 @@ int dcn_forward(c2m_stream_t stream, const float* input, const float* weight, co
                          nhwc ? 1 : 0, wt, (float*)nullptr);
   }
   if ((rc = check_launch()) != C2M_OK) return rc;
-  if (ext.f16x2 && (!ext.wt || !nhwc || gk.CPG < 16)) return C2M_ERR_UNSUPPORTED;
-  gk.range_flag = g.range_flag;
-  if (nhwc) {
+  const FwdArgs a = {st, nhwc ? inl : input, wt, bias, offset, mask, gk, output};
+  {
     ProfileScope prof(C2M_KERNEL_DCN_FWD, st);
-    if (ext.f16x2) {
-      if (split) rc = dispatch_fwd_nhwc<16, true, false, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, gk, output);
-      else if (g.CPG == 16) rc = dispatch_fwd_nhwc<16, false, false, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output);
-      else rc = dispatch_fwd_nhwc<32, false, false, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output);
-    } else if (bf16) {
-      if (split) rc = dispatch_fwd_nhwc<16, true, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, gk, output);
-      else if (g.CPG == 16) rc = dispatch_fwd_nhwc<16, false, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output);
-      else rc = dispatch_fwd_nhwc<32, false, true>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output);
-    } else if (split) {
-      rc = dispatch_fwd_nhwc<16, true, false>(st, fwd_mt(Co), inl, wt, bias, offset, mask, gk, output);
+    if (nhwc) {
+      rc = select_fwd_nhwc(a, ext.f16x2 ? F16X2 : bf16 ? BF16 : FP32, split);
+      if (rc != C2M_OK) return rc;
     } else {
-      switch (g.CPG) {
-        case 8: rc = dispatch_fwd_nhwc<8, false, false>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output); break;
-        case 16: rc = dispatch_fwd_nhwc<16, false, false>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output); break;
-        default: rc = dispatch_fwd_nhwc<32, false, false>(st, fwd_mt(Co), inl, wt, bias, offset, mask, g, output); break;
+      switch (fwd_mt(Co)) {
+        case 1: launch_fwd<1, 4>(a); break;
+        case 2: launch_fwd<2, 4>(a); break;
+        case 4: launch_fwd<4, 2>(a); break;
+        default: launch_fwd<8, 1>(a); break;
       }
-    }
-    if (rc != C2M_OK) return rc;
-  } else {
-    ProfileScope prof(C2M_KERNEL_DCN_FWD, st);
-    switch (fwd_mt(Co)) {
-      case 1: launch_fwd<1, 4>(st, input, wt, bias, offset, mask, g, output); break;
-      case 2: launch_fwd<2, 4>(st, input, wt, bias, offset, mask, g, output); break;
-      case 4: launch_fwd<4, 2>(st, input, wt, bias, offset, mask, g, output); break;
-      default: launch_fwd<8, 1>(st, input, wt, bias, offset, mask, g, output); break;
     }
   }
   return check_launch();
+}
+
+// the two channels-last entry points: the caller's bordered copy and weight image, output layout and activation
+FwdExt nhwc_ext(const float* input_bordered, int input_grouped, const void* wt, int out_nhwc, int out_pix_pitch,
+                int out_row_pitch, long long out_img_pitch, int act, float slope) {
+  FwdExt ext;
+  ext.inl = input_bordered; ext.in_grouped = input_grouped; ext.wt = static_cast<const float*>(wt); ext.out_nhwc = out_nhwc;
+  ext.out_pix_pitch = out_pix_pitch; ext.out_row_pitch = out_row_pitch; ext.out_img_pitch = out_img_pitch; ext.act = act;
+  ext.slope = slope;
+  return ext;
 }
 }  // namespace
 
@@ -1575,22 +1624,18 @@ extern "C" int c2m_nchw_to_nhwc_bordered_f32(c2m_stream_t stream, const float* i
 
 extern "C" size_t c2m_dcn_v2_relayout_bytes(int C, int Co, int kh, int kw, int dg) {
   Geom g;
-  if (make_geom(g, 1, C, 8, 8, Co, kh, kw, 1, 1, kh / 2, kw / 2, 1, 1, dg) != C2M_OK || !use_nhwc(g)) return 0;
-  return sizeof(float) * (size_t)g.KtotPad * copad_fwd(Co);
+  if (relayout_geom(g, C, Co, kh, kw, dg) != C2M_OK) return 0;
+  return sizeof(float) * (size_t)g.KtotPad * g.CoPad;
 }
 
 extern "C" int c2m_dcn_v2_relayout_f32(c2m_stream_t stream, const float* weight, int C, int Co, int kh, int kw, int dg,
                                        float* wt) {
   if (!weight || !wt) return C2M_ERR_INVALID_ARG;
   Geom g;
-  int rc = make_geom(g, 1, C, 8, 8, Co, kh, kw, 1, 1, kh / 2, kw / 2, 1, 1, dg);
+  const int rc = relayout_geom(g, C, Co, kh, kw, dg);
   if (rc != C2M_OK) return rc;
-  if (!use_nhwc(g)) return C2M_ERR_UNSUPPORTED;
-  g.CoPad = copad_fwd(Co);
-  Geom gk = g;
-  if (g.CPG == 8 && g.dg % 4 == 0) { gk.CPG = 2 * g.CPG; gk.dg = g.dg / 2; }
   hipLaunchKernelGGL(dcn::weight_relayout_kernel, dim3(ceil_div(g.CoPad * g.KtotPad, 256)), dim3(256), 0, as_stream(stream),
-                     weight, gk, 0, 1, wt, (float*)nullptr);
+                     weight, kernel_geom(g), 0, 1, wt, (float*)nullptr);
   return check_launch();
 }
 
@@ -1599,40 +1644,34 @@ extern "C" int c2m_dcn_v2_forward_nhwc_f32(c2m_stream_t stream, const float* inp
                                            int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                                            int dg, float* output, int out_nhwc, int out_pix_pitch, int out_row_pitch,
                                            long long out_img_pitch, int act, float slope, int input_grouped) {
-  FwdExt ext;
-  ext.inl = input_bordered; ext.in_grouped = input_grouped; ext.wt = wt; ext.out_nhwc = out_nhwc; ext.out_pix_pitch = out_pix_pitch;
-  ext.out_row_pitch = out_row_pitch; ext.out_img_pitch = out_img_pitch; ext.act = act; ext.slope = slope;
+  const FwdExt ext = nhwc_ext(input_bordered, input_grouped, wt, out_nhwc, out_pix_pitch, out_row_pitch, out_img_pitch, act, slope);
   return dcn_forward(stream, nullptr, nullptr, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
                      nullptr, 0, false, ext);
 }
 
 // ---- f16 x 2 GEMM (channels-last path, >= 16 channels per -- possibly virtual -- group)
-static bool f16x2_geom(Geom& g, Geom& gk, int C, int Co, int kh, int kw, int dg) {
-  if (make_geom(g, 1, C, 8, 8, Co, kh, kw, 1, 1, kh / 2, kw / 2, 1, 1, dg) != C2M_OK || !use_nhwc(g)) return false;
-  g.CoPad = copad_fwd(Co);
-  gk = g;
-  if (g.CPG == 8 && g.dg % 4 == 0) { gk.CPG = 2 * g.CPG; gk.dg = g.dg / 2; }
-  return gk.CPG >= 16 && g.Ktot % 16 == 0;
+static bool f16x2_geom(Geom& g, int C, int Co, int kh, int kw, int dg) {
+  return relayout_geom(g, C, Co, kh, kw, dg) == C2M_OK && kernel_geom(g).CPG >= 16 && g.Ktot % 16 == 0;
 }
 
 extern "C" size_t c2m_dcn_v2_relayout_f16x2_bytes(int C, int Co, int kh, int kw, int dg) {
-  Geom g, gk;
-  if (!f16x2_geom(g, gk, C, Co, kh, kw, dg)) return 0;
+  Geom g;
+  if (!f16x2_geom(g, C, Co, kh, kw, dg)) return 0;
   return (size_t)g.Ktot * g.CoPad * 4 + 256;   // two f16 pieces per weight + the float 1/S behind them
 }
 
 extern "C" int c2m_dcn_v2_relayout_f16x2(c2m_stream_t stream, const float* weight, int C, int Co, int kh, int kw, int dg,
                                          void* wt) {
   if (!weight || !wt) return C2M_ERR_INVALID_ARG;
-  Geom g, gk;
-  if (!f16x2_geom(g, gk, C, Co, kh, kw, dg)) return C2M_ERR_UNSUPPORTED;
+  Geom g;
+  if (!f16x2_geom(g, C, Co, kh, kw, dg)) return C2M_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   float* sinv = static_cast<float*>(wt) + (size_t)g.Ktot * g.CoPad;
   const long long n = (long long)Co * C * kh * kw;
   if (n > 0x7fffffffLL) return C2M_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(dcn::weight_absmax_kernel, dim3(1), dim3(1024), 0, st, weight, (int)n, sinv);
-  hipLaunchKernelGGL(dcn::weight_relayout_f16x2_kernel, dim3(ceil_div(g.CoPad * g.Ktot, 256)), dim3(256), 0, st, weight, gk, sinv,
-                     static_cast<_Float16*>(wt));
+  hipLaunchKernelGGL(dcn::weight_relayout_f16x2_kernel, dim3(ceil_div(g.CoPad * g.Ktot, 256)), dim3(256), 0, st, weight,
+                     kernel_geom(g), sinv, static_cast<_Float16*>(wt));
   return check_launch();
 }
 
@@ -1641,10 +1680,8 @@ extern "C" int c2m_dcn_v2_forward_nhwc_f16x2(c2m_stream_t stream, const float* i
                                              int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                                              int dg, float* output, int out_nhwc, int out_pix_pitch, int out_row_pitch,
                                              long long out_img_pitch, int act, float slope, int input_grouped, int* range_flag) {
-  FwdExt ext;
-  ext.inl = input_bordered; ext.in_grouped = input_grouped; ext.wt = static_cast<const float*>(wt); ext.out_nhwc = out_nhwc;
-  ext.out_pix_pitch = out_pix_pitch; ext.out_row_pitch = out_row_pitch; ext.out_img_pitch = out_img_pitch; ext.act = act;
-  ext.slope = slope; ext.f16x2 = 1; ext.range_flag = range_flag;
+  FwdExt ext = nhwc_ext(input_bordered, input_grouped, wt, out_nhwc, out_pix_pitch, out_row_pitch, out_img_pitch, act, slope);
+  ext.f16x2 = 1; ext.range_flag = range_flag;
   return dcn_forward(stream, nullptr, nullptr, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
                      nullptr, 0, false, ext);
 }
@@ -1666,24 +1703,6 @@ extern "C" int c2m_dcn_v2_forward_bf16mma_f32(c2m_stream_t stream, const float* 
 }
 
 namespace {
-template <int MT, bool NHWC>
-int launch_bwd_weight_l(hipStream_t st, dim3 grid, const float* in, const float* off, const float* msk, const float* go,
-                        const Geom& g, int chunks_per_b, int nsplit, float* gw) {
-  const size_t lds = sizeof(float) * (size_t)(MT * 32 + 32) * dcn::LDP;
-  static unsigned long long lds_set = 0;
-  if (lds > 48 * 1024)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&dcn::dcn_bwd_weight_kernel<MT, NHWC>), lds, lds_set)) return rc;
-  hipLaunchKernelGGL((dcn::dcn_bwd_weight_kernel<MT, NHWC>), grid, dim3(256), lds, st, in, off, msk, go, g, chunks_per_b, nsplit, gw);
-  return C2M_OK;
-}
-// `inl` != nullptr selects the channels-last variant (in = bordered copy)
-template <int MT>
-int launch_bwd_weight(hipStream_t st, dim3 grid, const float* in, const float* inl, const float* off, const float* msk,
-                      const float* go, const Geom& g, int chunks_per_b, int nsplit, float* gw) {
-  if (inl) return launch_bwd_weight_l<MT, true>(st, grid, inl, off, msk, go, g, chunks_per_b, nsplit, gw);
-  return launch_bwd_weight_l<MT, false>(st, grid, in, off, msk, go, g, chunks_per_b, nsplit, gw);
-}
-
 struct BwdWs {
   size_t wb, inl, total;
   int CoPad2;
@@ -1695,29 +1714,8 @@ inline BwdWs bwd_ws(const Geom& g) {
   w.nhwc = (g.CPG == 8 || g.CPG == 16 || g.CPG == 32) && g.C % 32 == 0;
   w.wb = 0;
   w.inl = align256(sizeof(float) * (size_t)(w.CoPad2 > 0 ? w.CoPad2 : 0) * g.KtotPad);
-  w.total = w.inl + (w.nhwc ? align256(sizeof(float) * (size_t)g.B * g.C * (g.H + 3) * (g.W + 3)) : 0);
+  w.total = w.inl + (w.nhwc ? bordered_copy_bytes(g.B, g.C, g.H, g.W) : 0);
   return w;
-}
-
-template <int COH, int CPG>
-int launch_bwd_offmask_cpg(hipStream_t st, dim3 grid, const float* inl, const float* wb, const float* off,
-                           const float* msk, const float* go, const Geom& g, float* goff, float* gmsk) {
-  const size_t lds = sizeof(float) * 2 * (size_t)(2 * COH) * 32;   // two staged Wb tiles
-  static unsigned long long lds_set = 0;
-  if (lds > 48 * 1024)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&dcn::dcn_bwd_offmask_kernel<COH, CPG>), lds, lds_set))
-      return rc;
-  hipLaunchKernelGGL((dcn::dcn_bwd_offmask_kernel<COH, CPG>), grid, dim3(256), lds, st, inl, wb, off, msk, go, g, goff, gmsk);
-  return C2M_OK;
-}
-template <int COH>
-int launch_bwd_offmask(hipStream_t st, dim3 grid, const float* inl, const float* wb, const float* off, const float* msk,
-                       const float* go, const Geom& g, float* goff, float* gmsk) {
-  switch (g.CPG) {
-    case 8: return launch_bwd_offmask_cpg<COH, 8>(st, grid, inl, wb, off, msk, go, g, goff, gmsk);
-    case 16: return launch_bwd_offmask_cpg<COH, 16>(st, grid, inl, wb, off, msk, go, g, goff, gmsk);
-    default: return launch_bwd_offmask_cpg<COH, 32>(st, grid, inl, wb, off, msk, go, g, goff, gmsk);
-  }
 }
 }  // namespace
 
@@ -1759,54 +1757,45 @@ extern "C" int c2m_dcn_v2_backward_f32(c2m_stream_t stream, const float* input, 
                      st, weight, g, ws.CoPad2, offmask ? 2 : 0, (float*)nullptr, wb);
   if ((rc = check_launch()) != C2M_OK) return rc;
   // zero-bordered channels-last copy of the input for the gathers of the offset/mask and weight kernels
-  float* inl = ws.nhwc ? reinterpret_cast<float*>(static_cast<char*>(workspace) + ws.inl) : nullptr;
   // (8-channel groups: group-major, as in the forward -- a 32-byte sample run then shares its line with its neighbours)
-  const bool bgrouped = inl && g.CPG == 8 && [] { const char* e = getenv("C2M_DCN_BWD_GROUPED"); return !(e && e[0] == '0'); }();
-  g.in_grouped = bgrouped ? 1 : 0;
-  if (inl) launch_nhwc_copy(st, input, B, C, H, W, inl, bgrouped);
-  if (offmask) {
+  float* inl = ws.nhwc ? reinterpret_cast<float*>(static_cast<char*>(workspace) + ws.inl) : nullptr;
+  g.in_grouped = (inl && g.CPG == 8) ? 1 : 0;
+  if (inl) launch_nhwc_copy(st, input, B, C, H, W, inl, g.in_grouped != 0);
+  const int nkt = g.KtotPad / 32;
+  {
     ProfileScope prof(C2M_KERNEL_DCN_BWD_DATA, st);
-    const int nkt = g.KtotPad / 32;
     int nz = ceil_div(2048, ceil_div(HWo, 128) * B);
     nz = nz < 1 ? 1 : (nz > nkt ? nkt : nz);
     dim3 grid(ceil_div(HWo, 128), B, nz);
-    switch (ws.CoPad2) {
-      case 64: rc = launch_bwd_offmask<32>(st, grid, inl, wb, offset, mask, grad_output, g, grad_offset, grad_mask); break;
-      case 128: rc = launch_bwd_offmask<64>(st, grid, inl, wb, offset, mask, grad_output, g, grad_offset, grad_mask); break;
-      default: rc = launch_bwd_offmask<128>(st, grid, inl, wb, offset, mask, grad_output, g, grad_offset, grad_mask); break;
-    }
+    with_constant<32, 64, 128>(ws.CoPad2 / 2, [&](auto coh_c) {   // each half of the 64 / 128 / 256 padded output channels
+      constexpr int COH = decltype(coh_c)::value;
+      if (offmask)
+        with_constant<8, 16, 32>(g.CPG, [&](auto cpg_c) {
+          const size_t lds = sizeof(float) * 2 * (size_t)(2 * COH) * 32;   // two staged Wb tiles
+          rc = launch_dynamic_lds<&dcn::dcn_bwd_offmask_kernel<COH, decltype(cpg_c)::value>>(
+              grid, lds, st, inl, wb, offset, mask, grad_output, g, grad_offset, grad_mask);
+        });
+      else
+        hipLaunchKernelGGL((dcn::dcn_bwd_data_kernel<COH>), grid, dim3(256), 0, st, input, wb, offset, mask, grad_output, g,
+                           grad_input, grad_offset, grad_mask);
+    });
     if (rc != C2M_OK) return rc;
-  } else {
-    ProfileScope prof(C2M_KERNEL_DCN_BWD_DATA, st);
-    const int nkt = g.KtotPad / 32;
-    int nz = ceil_div(2048, ceil_div(HWo, 128) * B);
-    nz = nz < 1 ? 1 : (nz > nkt ? nkt : nz);
-    dim3 grid(ceil_div(HWo, 128), B, nz);
-    switch (ws.CoPad2) {
-      case 64: hipLaunchKernelGGL((dcn::dcn_bwd_data_kernel<32>), grid, dim3(256), 0, st, input, wb, offset, mask, grad_output, g, grad_input, grad_offset, grad_mask); break;
-      case 128: hipLaunchKernelGGL((dcn::dcn_bwd_data_kernel<64>), grid, dim3(256), 0, st, input, wb, offset, mask, grad_output, g, grad_input, grad_offset, grad_mask); break;
-      default: hipLaunchKernelGGL((dcn::dcn_bwd_data_kernel<128>), grid, dim3(256), 0, st, input, wb, offset, mask, grad_output, g, grad_input, grad_offset, grad_mask); break;
-    }
   }
   if ((rc = check_launch()) != C2M_OK) return rc;
   {
     ProfileScope prof(C2M_KERNEL_DCN_BWD_WEIGHT, st);
     const int chunks_per_b = ceil_div(HWo, dcn::PCH);
-    const int nkt = g.KtotPad / 32;
     int nsplit = ceil_div(1024, nkt);
     if (nsplit > B * chunks_per_b) nsplit = B * chunks_per_b;
-    const int MT = g.CoPad / 32;
     dim3 grid(nkt, nsplit);
-    switch (MT) {
-      case 1: rc = launch_bwd_weight<1>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 2: rc = launch_bwd_weight<2>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 3: rc = launch_bwd_weight<3>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 4: rc = launch_bwd_weight<4>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 5: rc = launch_bwd_weight<5>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 6: rc = launch_bwd_weight<6>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      case 7: rc = launch_bwd_weight<7>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-      default: rc = launch_bwd_weight<8>(st, grid, input, inl, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight); break;
-    }
+    with_constant<1, 2, 3, 4, 5, 6, 7, 8>(g.CoPad / 32, [&](auto mt_c) {   // copad2() admitted Co <= 256
+      constexpr int MT = decltype(mt_c)::value;
+      const size_t lds = sizeof(float) * (size_t)(MT * 32 + 32) * dcn::LDP;
+      with_constant<0, 1>(inl != nullptr, [&](auto nhwc_c) {   // the channels-last variant gathers from the bordered copy
+        rc = launch_dynamic_lds<&dcn::dcn_bwd_weight_kernel<MT, decltype(nhwc_c)::value != 0>>(
+            grid, lds, st, inl ? inl : input, offset, mask, grad_output, g, chunks_per_b, nsplit, grad_weight);
+      });
+    });
     if (rc != C2M_OK) return rc;
   }
   if ((rc = check_launch()) != C2M_OK) return rc;

@@ -47,6 +47,13 @@ SHAPES = [
     (1, 24, 7, 8, 16, 3, 3, (1, 1), (1, 1), (1, 1), 3),       # odd group count: NCHW kernel
     (2, 64, 9, 10, 96, 3, 3, (2, 2), (1, 1), (1, 1), 2),      # 32-channel groups, Co = 96 (padded m-tiles), stride 2
 ]
+_S1 = ((1, 1), (1, 1), (1, 1))
+# Co = 24: one m-tile per wave (fwd_mt == 1) on the reduced arithmetics, 16- and 32-channel groups
+FWD_MT1_SHAPES = [(1, 32, 7, 9, 24, 3, 3, *_S1, 2), (1, 64, 7, 9, 24, 3, 3, *_S1, 2)]
+# Co = 160 / 192 / 224: the backward weight kernel's MT = CoPad / 32 = 5, 6, 7, planar (4-channel groups) and channels-last
+# (8-channel groups, C % 32 == 0) variant
+BWD_MT567_NHWC = [(1, 32, 5, 6, Co, 3, 3, *_S1, 4) for Co in (160, 192, 224)]
+BWD_MT567_SHAPES = [(1, 8, 5, 6, Co, 3, 3, *_S1, 2) for Co in (160, 192, 224)] + BWD_MT567_NHWC
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -82,7 +89,7 @@ def test_forward_nhwc_group_major_input(env, dev, shape):
                                atol=2e-5 * max(1.0, float(np.abs(want).max())))
 
 
-@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[1], SHAPES[2], SHAPES[7]])
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[1], SHAPES[2], SHAPES[7]] + FWD_MT1_SHAPES)
 def test_forward_bf16_mma_matches_bf16_oracle(env, dev, shape):
     """bf16-MFMA variant (fp32 tensors; staged input, weights and blended samples rounded to bf16, fp32 accumulation)
     against the ORACLE evaluated with exactly those roundings (oracle.dcn_v2_forward_bf16).  The only freedom left is the
@@ -135,7 +142,8 @@ def _dcn_ref64(x, w, b, off, msk, dg):
     return torch.einsum("ock,bckhw->bohw", w.reshape(w.shape[0], C, 9), cols) + b[None, :, None, None]
 
 
-@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[1], SHAPES[2], (2, 32, 13, 15, 64, 3, 3, (1, 1), (1, 1), (1, 1), 2)])
+@pytest.mark.parametrize("shape", [SHAPES[0], SHAPES[1], SHAPES[2], (2, 32, 13, 15, 64, 3, 3, (1, 1), (1, 1), (1, 1), 2)]
+                         + FWD_MT1_SHAPES)
 def test_forward_nhwc_f16x2_matches_oracle(env, dev, shape):
     """The f16 x 2 implicit GEMM (fp32 result on the f16 matrix pipe: blended samples and scaled weights in two f16 pieces,
     three products per k step) against the oracle, at the fp32 kernel's tolerance, and no further from a float64 evaluation
@@ -309,7 +317,7 @@ def test_backward_full_size_weight_grad_is_conv2d_grad(env, dev, C, H):
     assert float((gw2 - gw_ref).abs().max()) <= 5e-4 * max(1e-3, float(gw_ref.abs().max()))
 
 
-@pytest.mark.parametrize("shape", [s for s in SHAPES if (s[1] // s[10]) % 4 == 0])
+@pytest.mark.parametrize("shape", [s for s in SHAPES if (s[1] // s[10]) % 4 == 0] + BWD_MT567_SHAPES)
 def test_backward_matches_oracle(env, dev, shape):
     ops, oracle, synth = env
     B, C, H, W, Co, kh, kw, st, pd, dl, dg = shape
@@ -343,7 +351,8 @@ def test_backward_is_overwriting_not_accumulating(env, dev):
     (1, 256, 7, 9, 256, (1, 1), 8),    # 32: half a group per lane, cross-half add
     (2, 64, 9, 10, 96, (2, 2), 2),     # 32, stride 2, Co = 96
     (1, 48, 8, 9, 24, (1, 1), 6),      # C % 32 != 0: stays on the atomic kernel
-])
+    # 8, Co = 160 / 192 / 224: offset/mask kernel with 128 output channels per half, weight kernel MT = 5, 6, 7
+] + [(*s[:5], s[7], s[10]) for s in BWD_MT567_NHWC])
 def test_backward_without_input_grad(env, dev, cfg):
     """grad_input is optional at the C-ABI (NULL pointer).  The other four gradients must not change -- although
     grad_offset / grad_mask then come from a different kernel (dcn_bwd_offmask_kernel: channels-last gathers, plain
