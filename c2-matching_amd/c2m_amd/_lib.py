@@ -105,6 +105,8 @@ def _declare(L):
     L.c2m_contras_loss_forward_f32.argtypes = [_vp] * 5 + [_i] * 6 + [_vp] * 3 + [_i, _i] + [ctypes.c_float] * 3 + [_vp, _vp, _sz]
     L.c2m_contras_loss_rows_f32.argtypes = [_vp] + [_i] * 6 + [_vp, _sz] + [_vp] * 5
     L.c2m_contras_loss_backward_f32.argtypes = [_vp] + [_i] * 6 + [_vp] * 3 + [_i, _i] + [ctypes.c_float] * 3 + [_i] + [_vp] * 4 + [_sz]
+    L.c2m_warp_perspective_u8.argtypes = [_vp] * 4 + [_i] * 3 + [_vp] * 3
+    L.c2m_pil_bicubic_u8.argtypes = [_vp, _vp] + [_i] * 5 + [_vp] * 3 + [_i, _vp, _vp]
 
 
 def lib():

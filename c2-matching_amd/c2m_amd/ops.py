@@ -1510,3 +1510,149 @@ def contras_loss_rows(f1, f2, transformed_coordinates, margin=1.0, safe_radius=4
             "c2m_contras_loss_rows_f32")
     rows.update(corr)
     return rows
+
+
+# ---- training pairs of the extractor training (stages 1-2; csrc/contras_pairs.hip) ------------------------------------
+
+_PIL_PRECISION_BITS = 32 - 8 - 2
+
+
+def _dev_u8(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.C2MError(f"{name} must be a tensor on the GPU (the HIP path has no CPU fallback)")
+    if t.dtype != torch.uint8:
+        raise _lib.C2MError(f"{name} must be uint8, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _pil_bicubic_weight(x):
+    a = -0.5
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_bicubic_tables(in_size, out_size):
+    """Pillow's fixed-point bicubic coefficients for resampling one axis from in_size to out_size (Resample.c:
+    precompute_coeffs + normalize_coeffs_8bpc, 22 fraction bits), in banded form: (start [out] int32, count [out] int32,
+    coeff [out, K] int32 with K = the largest count, rows padded with zeros).  Row i weighs input pixels
+    start[i] .. start[i] + count[i] - 1.  Host tensors; the same numbers as the non-zero band of
+    mmsr.data.pil_bicubic._coeff_matrix."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError("sizes must be positive")
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 2.0 * filterscale
+    ss = 1.0 / filterscale
+    rows, starts = [], []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        w = [_pil_bicubic_weight((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        row = []
+        for v in w:
+            k = v / ww if ww != 0.0 else v
+            row.append(int(-0.5 + k * (1 << _PIL_PRECISION_BITS)) if k < 0 else int(0.5 + k * (1 << _PIL_PRECISION_BITS)))
+        # the kernel accumulates in int32: 255 * sum |c| plus the rounding constant must fit
+        if 255 * sum(abs(c) for c in row) + (1 << (_PIL_PRECISION_BITS - 1)) >= 1 << 31:
+            raise _lib.C2MError(f"pil_bicubic_tables({in_size}, {out_size}): row {xx} can overflow an int32 accumulator")
+        rows.append(row)
+        starts.append(xmin)
+    K = max(1, max(len(r) for r in rows))
+    coeff = torch.zeros((out_size, K), dtype=torch.int32)
+    for i, r in enumerate(rows):
+        if r:
+            coeff[i, :len(r)] = torch.tensor(r, dtype=torch.int32)
+    return (torch.tensor(starts, dtype=torch.int32), torch.tensor([len(r) for r in rows], dtype=torch.int32), coeff)
+
+
+_pil_tables = {}
+_pil_tables_lock = threading.Lock()
+
+
+def _pil_tables_on(in_size, out_size, device):
+    key = (int(in_size), int(out_size), str(device))
+    with _pil_tables_lock:
+        if key not in _pil_tables:
+            _pil_tables[key] = tuple(t.to(device) for t in pil_bicubic_tables(in_size, out_size))
+        return _pil_tables[key]
+
+
+def _pil_pass(x, vertical, out_size, as_float):
+    N, (H, W) = x.numel() // (x.shape[-2] * x.shape[-1]), x.shape[-2:]
+    start, count, coeff = _pil_tables_on(H if vertical else W, out_size, x.device)
+    shape = tuple(x.shape[:-2]) + ((out_size, W) if vertical else (H, out_size))
+    out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    outf = torch.empty(shape, dtype=torch.float32, device=x.device) if as_float else None
+    _lib.check(_lib.lib().c2m_pil_bicubic_u8(_stream(), x.data_ptr(), N, H, W, int(vertical), int(out_size), start.data_ptr(),
+                                             count.data_ptr(), coeff.data_ptr(), coeff.shape[1], out.data_ptr(),
+                                             outf.data_ptr() if as_float else None), "c2m_pil_bicubic_u8")
+    return out, outf
+
+
+def pil_bicubic_resize_u8(img_u8, out_h, out_w, as_float=False):
+    """img_u8: uint8 [..., H, W] on the GPU -> uint8 [..., out_h, out_w], identical to ``PIL.Image.resize((out_w, out_h),
+    Image.BICUBIC)`` per plane (and to mmsr.data.pil_bicubic.pil_bicubic_resize): a horizontal and a vertical launch in
+    Pillow's integer arithmetic with the uint8 intermediate between them; an axis whose size does not change is skipped.
+    as_float: -> (uint8, float32 = uint8 / 255 exactly), the float image written by the last pass (when no axis changes
+    size, by one pass with the identity table)."""
+    x = _dev_u8(img_u8, "img_u8")
+    if x.dim() < 2 or x.numel() == 0:
+        raise _lib.C2MError("img_u8 must be a non-empty [..., H, W] tensor")
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h <= 0 or out_w <= 0:
+        raise _lib.C2MError("out_h / out_w must be positive")
+    H, W = x.shape[-2:]
+    passes = [(False, out_w)] if W != out_w else []
+    if H != out_h:
+        passes.append((True, out_h))
+    if not passes:
+        if not as_float:
+            return x.clone()
+        passes = [(False, W)]
+    xf = None
+    with torch.cuda.device(x.device):
+        for k, (vertical, size) in enumerate(passes):
+            x, xf = _pil_pass(x, vertical, size, as_float and k == len(passes) - 1)
+    return (x, xf) if as_float else x
+
+
+def warp_perspective_u8(src_u8, M):
+    """The reference's ``cv2.warpPerspective(img, H_inverse, (W, H))`` and its transformed-coordinate grid for a batch.
+
+    src_u8 [B,3,H,W] uint8 on the GPU; M [B,3,3] (or [3,3], used for every sample): float64 array or tensor, the matrix
+    handed to warpPerspective (the reference's H_inverse).  It is inverted here, on the host, in float64.
+    -> (dst_f32 [B,3,H,W] in [0,1], dst_u8 = trunc(dst_f32 * 255), coords [B,H,W,3] float64 = M.(x, y, 1) / third component).
+    Bilinear on a 1/32-pixel position grid with a constant zero border (include/c2m_hip.h states the rule); parity with
+    OpenCV unpinned."""
+    import numpy as np
+    src = _dev_u8(src_u8, "src_u8")
+    if src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0:
+        raise _lib.C2MError("src_u8 must be [B,3,H,W]")
+    B, _, H, W = src.shape
+    m = np.asarray(M.detach().cpu() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
+    if m.shape == (3, 3):
+        m = np.broadcast_to(m, (B, 3, 3))
+    if m.shape != (B, 3, 3) or not np.isfinite(m).all():
+        raise _lib.C2MError(f"M must be {B} finite 3x3 matrices, got shape {m.shape}")
+    try:
+        mi = np.linalg.inv(m)
+    except np.linalg.LinAlgError as e:
+        raise _lib.C2MError(f"M is not invertible: {e}")
+    mats = torch.from_numpy(np.ascontiguousarray(np.stack([m, mi]))).to(src.device)
+    dst_f32 = torch.empty((B, 3, H, W), dtype=torch.float32, device=src.device)
+    dst_u8 = torch.empty((B, 3, H, W), dtype=torch.uint8, device=src.device)
+    coords = torch.empty((B, H, W, 3), dtype=torch.float64, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().c2m_warp_perspective_u8(_stream(), src.data_ptr(), mats[0].data_ptr(), mats[1].data_ptr(), B, H, W,
+                                                      dst_f32.data_ptr(), dst_u8.data_ptr(), coords.data_ptr()),
+                   "c2m_warp_perspective_u8")
+    return dst_f32, dst_u8, coords

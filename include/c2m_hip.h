@@ -426,6 +426,34 @@ int c2m_contras_loss_rows_f32(c2m_stream_t stream, int B, int C, int H1, int W1,
                               const void* workspace, size_t workspace_bytes, float* pos, float* neg1, int* neg1_idx,
                               float* neg2, int* neg2_idx);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training pairs of the extractor training, stages 1-2 (contras_pairs.hip): what mmsr/data/contras_dataset.py:13-92,
+ * 150-229 builds per sample on the host (cv2.warpPerspective, the float64 coordinate grid, four PIL bicubic resizes),
+ * for a whole batch of uint8 crops on the device.
+ *
+ * c2m_warp_perspective_u8: src [B][3][H][W] uint8 planar; M, M_inv [B][3][3] float64 (DEVICE; M is the matrix the
+ * reference passes to cv2.warpPerspective, its H_inverse; M_inv = inv(M), inverted by the caller in float64).
+ *   dst_f32 [B][3][H][W] in [0, 1]: for destination pixel (x, y), (X, Y, Wd) = M_inv . (x, y, 1) in float64,
+ *     sx = rint(32 X / Wd), sy = rint(32 Y / Wd) (half to even, saturated to int32; 0 when Wd == 0), x0 = sx >> 5,
+ *     a = (sx & 31) / 32, likewise y0, b;  dst = s00 (1-a)(1-b) + s01 a(1-b) + s10 (1-a)b + s11 ab in fp32 in that order,
+ *     s = u8 / 255 in fp32, taps outside the image 0.  Meant as OpenCV's INTER_LINEAR with BORDER_CONSTANT; parity with
+ *     OpenCV is unpinned.
+ *   dst_u8 [B][3][H][W] = trunc(dst_f32 * 255.0f): the reference's (img * 255).astype(np.uint8).
+ *   coords [B][H][W][3] float64 = M . (x, y, 1) divided by its third component.
+ * B * 3 * H * W < 2^31 (else C2M_ERR_UNSUPPORTED).
+ *
+ * c2m_pil_bicubic_u8: one axis of Pillow's 8-bit resampler (Resample.c) on N planes src [N][H][W] uint8:
+ *   vertical == 0: dst [N][H][out_size], vertical != 0: dst [N][out_size][W].  For output index i the caller supplies the
+ *   window start[i], the tap count[i] (start[i] + count[i] <= the axis' input size) and coeff [out_size][K] int32 with 22
+ *   fraction bits (rows padded with zeros, K >= every count): dst = clip8((2^21 + sum_k coeff[i][k] * p[start[i] + k]) >> 22).
+ *   255 * sum_k |coeff[i][k]| + 2^21 must stay below 2^31 (Pillow's bicubic tables do).  dst_f32 (same shape as dst_u8, or
+ *   NULL): the same pixels as fp32 p / 255.
+ */
+int c2m_warp_perspective_u8(c2m_stream_t stream, const uint8_t* src, const double* M, const double* M_inv, int B, int H,
+                            int W, float* dst_f32, uint8_t* dst_u8, double* coords);
+int c2m_pil_bicubic_u8(c2m_stream_t stream, const uint8_t* src, int N, int H, int W, int vertical, int out_size,
+                       const int* start, const int* count, const int* coeff, int K, uint8_t* dst_u8, float* dst_f32);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,11 @@
 """Times the stage-2 contrastive loss (forward + backward) and a whole stage-2 training step on two paths: the fused
 gfx950 kernel (c2m_amd.ops.contras_loss) and a per-sample torch restatement of the reference's loss written below.
 
-    python scripts/bench_contras.py [--steps 20] [--warmup 5] [--batch 8] [--size 160]
+    python scripts/bench_contras.py [--steps 20] [--warmup 5] [--batch 8] [--size 160] [--pairs synthetic|generated]
+
+--pairs generated: the batch of the training step comes from mmsr.data.contras_pairs.ContrasPairGenerator (smooth random
+uint8 images, drawn homographies) instead of random tensors with synthetic coordinates, and the generator is timed next
+to the stock-torch composition it replaces (torch_pairs below).
 
 Prints one JSON line per measurement (milliseconds, median over --steps after --warmup)."""
 import argparse
@@ -65,6 +69,39 @@ def coords_for(B, h, w, dev, seed=1):
     return torch.stack(out).to(dev)
 
 
+def smooth_images(B, size, dev, seed=2):
+    """uint8 [B,3,size,size]: low-frequency random images (random 10x10 fields, bicubic x16)."""
+    g = torch.Generator().manual_seed(seed)
+    low = torch.rand(B, 3, max(size // 16, 2), max(size // 16, 2), generator=g)
+    img = F.interpolate(low, size=(size, size), mode="bicubic", align_corners=False).clamp(0, 1)
+    return (img * 255).to(torch.uint8).to(dev)
+
+
+def torch_pairs(img_u8, matrices, scale=4):
+    """What ContrasPairGenerator replaces, composed from stock torch ops on the device: the float64 coordinate grid, a
+    grid_sample warp (bilinear, zero padding) and mmsr.data.pil_bicubic.pil_bicubic_resize for the four resizes."""
+    from mmsr.data.pil_bicubic import pil_bicubic_resize
+    B, _, H, W = img_u8.shape
+    dev = img_u8.device
+    M = torch.as_tensor(matrices, dtype=torch.float64).to(dev)
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64, device=dev), torch.arange(W, dtype=torch.float64, device=dev),
+                            indexing="ij")
+    grid = torch.stack([xs, ys, torch.ones_like(xs)], -1).reshape(1, -1, 3)
+    tc = grid @ M.transpose(1, 2)
+    coords = (tc / tc[..., 2:3]).reshape(B, H, W, 3)
+    sp = grid @ torch.linalg.inv(M).transpose(1, 2)
+    sp = sp[..., :2] / sp[..., 2:3]
+    norm = (sp + 0.5) / torch.tensor([W, H], dtype=torch.float64, device=dev) * 2 - 1
+    img = img_u8.float() / 255
+    ref = F.grid_sample(img, norm.float().reshape(B, H, W, 2), mode="bilinear", padding_mode="zeros", align_corners=False)
+    both = torch.cat([img_u8, (ref * 255).to(torch.uint8)])
+    lq = pil_bicubic_resize(both, H // scale, W // scale)
+    up = pil_bicubic_resize(lq, H, W).float() / 255
+    lq = lq.float() / 255
+    return {"img_in": img, "img_in_lq": lq[:B], "img_in_up": up[:B], "img_ref": ref, "img_ref_lq": lq[B:],
+            "img_ref_up": up[B:], "transformed_coordinate": coords}
+
+
 def timed(fn, steps, warmup):
     for _ in range(warmup):
         fn()
@@ -87,6 +124,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--size", type=int, default=160)
+    ap.add_argument("--pairs", choices=("synthetic", "generated"), default="synthetic")
     a = ap.parse_args()
     from c2m_amd import ops
     import mmsr.models as models
@@ -120,9 +158,24 @@ def main():
            "train": {"lr_g": 1e-4, "margin": 1.0, "safe_radius": 4, "scaling_steps": 2, "temperature": 0.15,
                      "distill_weight": 15}}
     model = models.create_model(opt)
-    img = torch.rand(B, 3, a.size, a.size)
-    model.feed_data({"img_in": img, "img_in_up": img, "img_ref": torch.rand(B, 3, a.size, a.size),
-                     "transformed_coordinate": coords.cpu()})
+    if a.pairs == "generated":
+        import numpy as np
+        from mmsr.data.contras_pairs import ContrasPairGenerator, sample_pair_homography
+        imgs = smooth_images(B, a.size, dev)
+        gen = ContrasPairGenerator(seed=0)
+        rs = np.random.RandomState(0)
+        mats = np.stack([sample_pair_homography(rs, (a.size, a.size))[1] for _ in range(B)])
+        for name, fn in (("generator", lambda: gen(imgs)), ("torch", lambda: torch_pairs(imgs, mats))):
+            print(json.dumps({"what": "pair_generation", "path": name, "B": B, "crop": a.size,
+                              "ms": round(timed(fn, a.steps, a.warmup), 3)}))
+        batch = gen(imgs)
+        print(json.dumps({"what": "generated_batch", "rows_per_sample":
+                          ops.contras_correspondences(batch["transformed_coordinate"], h, h)["counts"]}))
+        model.feed_data(batch)
+    else:
+        img = torch.rand(B, 3, a.size, a.size)
+        model.feed_data({"img_in": img, "img_in_up": img, "img_ref": torch.rand(B, 3, a.size, a.size),
+                         "transformed_coordinate": coords.cpu()})
     fused_loss = model.loss_function
     for name in ("fused", "torch"):
         if name == "torch":
@@ -132,7 +185,7 @@ def main():
         else:
             model.loss_function = fused_loss
         ms = timed(lambda: model.optimize_parameters(0), a.steps, a.warmup)
-        print(json.dumps({"what": "stage2_train_step", "path": name, "B": B, "crop": a.size, "ms": round(ms, 3)}))
+        print(json.dumps({"what": "stage2_train_step", "path": name, "pairs": a.pairs, "B": B, "crop": a.size, "ms": round(ms, 3)}))
 
 
 if __name__ == "__main__":
