@@ -89,7 +89,8 @@ def test_batched_samples_are_independent(env, dev):
 def test_exact_ties_across_x_tiles_and_rows(env, dev):
     """A ref map that repeats with period 12 horizontally and 10 vertically: every patch has exact duplicates in other
     28-column x-tiles of the sweep (visited later, some with LOWER index) and in other rows.  The reference's
-    "first maximum" (lowest flat index) must win whichever tile finds it -- for both row-DMA flavours."""
+    "first maximum" (lowest flat index) must win whichever tile finds it -- for both row-DMA flavours.  This test never looks at
+    the filter's tables; tests/test_corr_rescore_gpu.py reaches the deferred re-score paths on purpose and asserts they were taken."""
     ops, oracle, synth = env
     for wr in (72, 70):   # 72: dwordx4 row DMA, 70: dword row DMA
         fi = oracle.feature_normalize(synth.gaussish((256, 20, 21), 51))
