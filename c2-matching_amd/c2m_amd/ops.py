@@ -103,7 +103,7 @@ def feature_match_index_batched(feat_in, feat_ref, patch_size=3, input_stride=1,
                                                          ss_i.data_ptr() if ss_i is not None else None,
                                                          ss_r.data_ptr() if ss_r is not None else None),
                        "c2m_feature_match_index_pre_f32")
-        mfma = (not force_generic) and p == 3 and si == 1 and sr == 1 and C in (64, 128, 256)   # the C-ABI's own dispatch rule
+        mfma = (not force_generic) and p == 3 and si == 1 and sr == 1 and C in (64, 128, 256)   # restates mfma_channels() of csrc/corr_filter.h
         if return_skip or _corr_diag.enabled:
             # diagnostics only (bench.py's swept-row count, the dedup tests): the duplicate-row table exists only when the
             # MFMA kernel ran; nothing is kept otherwise, so the workspace dies with the call and no module state is
@@ -134,7 +134,7 @@ _corr_diag = _CorrDiag()
 
 class record_corr_skip_table:
     def __enter__(self):
-        _corr_diag.enabled, _corr_diag.table = True, None
+        _corr_diag.enabled, _corr_diag.table, _corr_diag.filter = True, None, None
         return self
 
     def __exit__(self, *exc):

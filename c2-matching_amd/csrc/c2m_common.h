@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/c2m_hip.h"
 
 namespace c2m {
@@ -46,6 +48,24 @@ inline int ensure_dynamic_lds(const void* fn, size_t bytes, unsigned long long& 
   }
   if (dev >= 0 && dev < 64) done |= 1ull << dev;
   return C2M_OK;
+}
+
+// Launch a kernel of THREADS threads with `lds` bytes of dynamic LDS; above the 48 KiB a kernel gets by default its limit is
+// raised first (once per device: `lds_set` is this instantiation's, that is this kernel's, flag).  static: the instantiations'
+// names carry the kernel's whole signature and would otherwise all land in the library's dynamic symbol table.
+template <auto Kernel, int THREADS = 256, typename... Args>
+static int launch_dynamic_lds(dim3 grid, size_t lds, hipStream_t st, Args... args) {
+  static unsigned long long lds_set = 0;
+  if (lds > 48 * 1024)
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds, lds_set)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, dim3(THREADS), lds, st, args...);
+  return C2M_OK;
+}
+
+// f(std::integral_constant<int, V>()) for the V of the list that equals v: turns a run-time choice into a template argument
+template <int... Vs, typename F>
+inline bool with_constant(int v, F&& f) {
+  return ((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
 }
 
 inline hipStream_t as_stream(c2m_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

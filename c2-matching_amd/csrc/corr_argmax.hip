@@ -199,18 +199,7 @@ __global__ void __launch_bounds__(256) corr_argmax_generic_kernel(
 // ------------------------------------------------------------------------------------------------------------------
 // MFMA sliding-window kernel (patch 3, strides 1)
 // ------------------------------------------------------------------------------------------------------------------
-namespace corr {
-constexpr int TQ = 16;            // query tile side, pixels
-constexpr int TPQ = TQ - 2;       // query patches per tile side (14)
-constexpr int WT = 32;            // ref x-tile width, pixels (= MFMA N)
-constexpr int WP = 28;            // ref patches per x-tile; a multiple of 4 keeps every tile origin 16-byte aligned
-                                  // for the dwordx4 row DMA (30 of the 32 loaded pixel columns are used)
-constexpr int NWAVE = 8;
-constexpr int NTHR = NWAVE * 64;
-constexpr int QPIX = TQ * TQ;     // 256 query pixels per tile
-constexpr int SLAB = QPIX * WT;   // floats per ring slab
-constexpr int NIT = TPQ;          // 14 tap-sum rounds: round `it` = query patch ROW it, half-wave (w, hi) = patch column 2w + hi
-}  // namespace corr
+// (tile geometry: namespace corr in corr_filter.h, shared with the pre-filter)
 
 // DMA16: ref rows are fetched with global_load_lds_dwordx4 (needs Wr % 4 == 0 and a 16-byte aligned ref base); otherwise
 // one dword per lane.
@@ -526,10 +515,10 @@ extern "C" int c2m_feature_normalize_ss_f32(c2m_stream_t stream, const float* x,
   if (!x || !out || B <= 0 || C <= 0 || HW <= 0) return C2M_ERR_INVALID_ARG;
   dim3 grid(ceil_div(HW, 256), B);
   hipStream_t st = as_stream(stream);
-  if (C == 256) hipLaunchKernelGGL(feature_normalize_reg_kernel<256>, grid, dim3(256), 0, st, x, HW, out, ss_out);
-  else if (C == 128) hipLaunchKernelGGL(feature_normalize_reg_kernel<128>, grid, dim3(256), 0, st, x, HW, out, ss_out);
-  else if (C == 64) hipLaunchKernelGGL(feature_normalize_reg_kernel<64>, grid, dim3(256), 0, st, x, HW, out, ss_out);
-  else hipLaunchKernelGGL(feature_normalize_kernel, grid, dim3(256), 0, st, x, C, HW, out, ss_out);
+  const bool reg = with_constant<64, 128, 256>(C, [&](auto c) {   // the channel column fits the registers
+    hipLaunchKernelGGL(feature_normalize_reg_kernel<decltype(c)::value>, grid, dim3(256), 0, st, x, HW, out, ss_out);
+  });
+  if (!reg) hipLaunchKernelGGL(feature_normalize_kernel, grid, dim3(256), 0, st, x, C, HW, out, ss_out);
   return check_launch();
 }
 
@@ -540,56 +529,69 @@ extern "C" int c2m_feature_normalize_f32(c2m_stream_t stream, const float* x, in
 namespace {
 struct CorrWs {
   size_t ss_ref, inv, ss_in, qden, row_eq, skip, total;  // byte offsets
-  int nxt;
+  int nxt;               // ref x-tiles: rows of `skip`, of `row_eq` and of the filter's `rimg`
   c2m::corrf::Ws f;   // scratch of the pre-filter path (corr_filter.h)
 };
-inline size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 inline CorrWs corr_ws(int B, int Hq, int Wq, int Hr, int Wr, int C = c2m::corrf::CMAX) {
+  using c2m::corr::align256;
   CorrWs w;
   size_t o = 0;
   w.ss_ref = o; o = align256(o + sizeof(float) * (size_t)B * Hr * Wr);
   w.inv = o;    o = align256(o + sizeof(float) * (size_t)B * Hr * Wr);
   w.ss_in = o;  o = align256(o + sizeof(float) * (size_t)B * Hq * Wq);
   w.qden = o;   o = align256(o + sizeof(float) * (size_t)B * Hq * Wq);
-  w.nxt = Wr > 2 ? (Wr - 2 + c2m::corr::WP - 1) / c2m::corr::WP : 1;
+  w.nxt = c2m::corr::x_tiles(Wr);
   w.row_eq = o; o = align256(o + sizeof(int) * (size_t)B * w.nxt * Hr);
   w.skip = o;   o = align256(o + sizeof(int2) * (size_t)B * w.nxt);
-  w.f = c2m::corrf::workspace(o, B, Hq, Wq, Hr, Wr, C);
+  w.f = c2m::corrf::workspace(o, B, Hq, Wq, Hr, Wr, w.nxt, C);
   w.total = w.f.total;
   return w;
 }
 
+// Patch norms of one map: per-pixel sums of squares into `ss` unless the caller brought them (ss_pre:
+// c2m_feature_normalize_ss_f32 forms them, same chain, while the normalised values are still in registers -- instead of a
+// pass over the map), then the patch norms over them.  invert: see patch_norm_kernel.
+int launch_patch_norms(hipStream_t st, const float* feat, const float* ss_pre, float* ss, int B, int C, int H, int W, int patch,
+                       int stride, int invert, float* out) {
+  const int Hp = (H - patch) / stride + 1, Wp = (W - patch) / stride + 1;
+  if (!ss_pre) hipLaunchKernelGGL(pixel_sumsq_kernel, dim3(ceil_div(H * W, 256), B), dim3(256), 0, st, feat, C, H * W, ss);
+  hipLaunchKernelGGL(patch_norm_kernel, dim3(ceil_div(Hp * Wp, 256), B), dim3(256), 0, st, ss_pre ? ss_pre : ss, H, W, patch,
+                     stride, Hp, Wp, invert, out);
+  return check_launch();
+}
+
+// The row DMA moves 16 bytes per lane where every row segment is 16-byte aligned: tile origins are multiples of WP = 28
+// pixels, so that takes Wr % 4 == 0 and an aligned ref base; otherwise one dword per lane.
+inline bool ref_rows_dma16(const float* fref, int Wr) {
+  return Wr % 4 == 0 && reinterpret_cast<uintptr_t>(fref) % 16 == 0;
+}
+
+// fws != nullptr: pre-filter + exact re-score first (wsbase: the workspace fws' offsets refer to, qden_buf: the query patch
+// norms it needs whatever norm_input says); the exact sweep then runs only if the filter's preparation raised its flag.
 template <int C>
-int launch_corr_mfma(hipStream_t st, const float* fin, const float* fref, int B, int Hq, int Wq, int Hr, int Wr,
-                     const float* inv, const float* qden, int* row_eq, int2* skip, int dedup, int64_t* max_idx,
-                     float* max_val, const c2m::corrf::Ws* fws = nullptr, char* wsbase = nullptr, const float* qden_buf = nullptr) {
+int launch_corr_mfma(hipStream_t st, const float* fin, const float* fref, int B, int Hq, int Wq, int Hr, int Wr, int nxt,
+                     const float* inv, const float* qden, int* row_eq, int2* skip, int64_t* max_idx, float* max_val,
+                     const c2m::corrf::Ws* fws, char* wsbase, const float* qden_buf) {
   using namespace c2m::corr;
-  const int tiles_y = ceil_div(Hq - 2, TPQ), tiles_x = ceil_div(Wq - 2, TPQ);
+  const QueryTiles tiles = query_tiles(Hq, Wq);
   const size_t lds = sizeof(float) * (size_t)(3 * SLAB + 2 * C * WT);
-  static unsigned long long lds_set[2] = {0, 0};
-  const bool dma16 = (Wr % 4 == 0) && (reinterpret_cast<uintptr_t>(fref) % 16 == 0);
-  auto kern = dma16 ? &corr_argmax_mfma_kernel<C, true> : &corr_argmax_mfma_kernel<C, false>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set[dma16])) return rc;
-  dim3 grid(B * tiles_y * tiles_x);
-  const int nxt = ceil_div(Wr - 2, WP);
-  if (dedup) {
-    hipLaunchKernelGGL(ref_row_equal_kernel, dim3(Hr - 1, nxt, B), dim3(256), 0, st, fref, C, Hr, Wr, nxt, row_eq);
-  } else {
-    (void)hipMemsetAsync(row_eq, 0, sizeof(int) * (size_t)B * nxt * Hr, st);
-  }
+  hipLaunchKernelGGL(ref_row_equal_kernel, dim3(Hr - 1, nxt, B), dim3(256), 0, st, fref, C, Hr, Wr, nxt, row_eq);
   hipLaunchKernelGGL(ref_row_run_kernel, dim3(ceil_div(B * nxt, 64)), dim3(64), 0, st, row_eq, Hr, B * nxt, skip);
   const int* need = nullptr;
   if (fws) {
-    // pre-filter + exact re-score; the sweep below then runs only if the filter's preparation raised its flag
-    if (int rc = c2m::corrf::launch(st, fin, fref, B, C, Hq, Wq, Hr, Wr, inv, qden_buf, qden ? 1 : 0, skip, wsbase, *fws, max_idx,
-                                    max_val))
+    if (int rc = c2m::corrf::launch(st, fin, fref, B, C, Hq, Wq, Hr, Wr, nxt, inv, qden_buf, qden ? 1 : 0, skip, wsbase, *fws,
+                                    max_idx, max_val))
       return rc;
     need = reinterpret_cast<const int*>(wsbase + fws->flags);
   }
   ProfileScope prof(C2M_KERNEL_CORR_MFMA, st);
-  hipLaunchKernelGGL(kern, grid, dim3(NTHR), lds, st, fin, fref, Hq, Wq, Hr, Wr, tiles_y, tiles_x, inv ? inv : fin,
-                     qden ? qden : fin, inv ? 1 : 0, qden ? 1 : 0, skip, need, max_idx, max_val);
-  return check_launch();
+  int rc = C2M_OK;
+  with_constant<0, 1>(ref_rows_dma16(fref, Wr), [&](auto dma16) {
+    rc = launch_dynamic_lds<&corr_argmax_mfma_kernel<C, decltype(dma16)::value != 0>, NTHR>(
+        dim3(B * tiles.y * tiles.x), lds, st, fin, fref, Hq, Wq, Hr, Wr, tiles.y, tiles.x, inv ? inv : fin, qden ? qden : fin,
+        inv ? 1 : 0, qden ? 1 : 0, skip, need, max_idx, max_val);
+  });
+  return rc != C2M_OK ? rc : check_launch();
 }
 }  // namespace
 
@@ -621,7 +623,7 @@ extern "C" size_t c2m_feature_match_workspace_bytes(int B, int Hq, int Wq, int H
 }
 
 // channels the pre-filter's per-channel scratch is laid out for: C where the filter has a kernel, else none
-static int filter_channels(int C) { return (C == 64 || C == 128 || C == 256) ? C : 0; }
+static int filter_channels(int C) { return c2m::corr::mfma_channels(C) ? C : 0; }
 
 extern "C" size_t c2m_feature_match_workspace_bytes_c(int B, int C, int Hq, int Wq, int Hr, int Wr) {
   if (B <= 0 || C <= 0 || Hq <= 0 || Wq <= 0 || Hr <= 0 || Wr <= 0) return 0;
@@ -662,21 +664,10 @@ extern "C" int c2m_feature_match_index_pre_f32(c2m_stream_t stream, const float*
   float* ss_in = reinterpret_cast<float*>(wsb + ws.ss_in);
   float* qden = reinterpret_cast<float*>(wsb + ws.qden);
 
-  const int Hqp = (Hq - patch) / in_stride + 1, Wqp = (Wq - patch) / in_stride + 1;
-  const int Hrp = (Hr - patch) / ref_stride + 1, Wrp = (Wr - patch) / ref_stride + 1;
-  int rc;
-  if (is_norm) {
-    // (ss_*_pre: per-pixel sums of squares the caller already holds -- c2m_feature_normalize_ss_f32 forms them, same chain, while
-    // the normalised values are still in registers -- instead of a pass over the map each)
-    if (!ss_ref_pre)
-      hipLaunchKernelGGL(pixel_sumsq_kernel, dim3(ceil_div(Hr * Wr, 256), B), dim3(256), 0, st, feat_ref, C, Hr * Wr,
-                         ss_ref);
-    hipLaunchKernelGGL(patch_norm_kernel, dim3(ceil_div(Hrp * Wrp, 256), B), dim3(256), 0, st, ss_ref_pre ? ss_ref_pre : ss_ref, Hr, Wr, patch,
-                       ref_stride, Hrp, Wrp, 1, inv);
-    if ((rc = check_launch()) != C2M_OK) return rc;
-  }
-  const bool fast = !force_generic && patch == 3 && in_stride == 1 && ref_stride == 1 &&
-                    (C == 64 || C == 128 || C == 256);
+  int rc = C2M_OK;
+  if (is_norm && (rc = launch_patch_norms(st, feat_ref, ss_ref_pre, ss_ref, B, C, Hr, Wr, patch, ref_stride, 1, inv)) != C2M_OK)
+    return rc;
+  const bool fast = !force_generic && patch == 3 && in_stride == 1 && ref_stride == 1 && c2m::corr::mfma_channels(C);
   // The pre-filter path (corr_filter.hip): 3/16 of the matrix time, same results.  It needs the ref-patch normalisation
   // (its error bound is relative to |r|) and shapes its 16-bit candidate codes cover.  $C2M_CORR_FILTER=0: exact sweep only.
   static const int filter_env = [] {
@@ -685,34 +676,23 @@ extern "C" int c2m_feature_match_index_pre_f32(c2m_stream_t stream, const float*
   }();
   const int filter_on = g_filter_mode < 0 ? filter_env : g_filter_mode;
   const bool use_filter = fast && filter_on && is_norm && c2m::corrf::shapes_ok(B, C, Hq, Wq, Hr, Wr);
-  if (norm_input || use_filter) {
-    if (!ss_in_pre)
-      hipLaunchKernelGGL(pixel_sumsq_kernel, dim3(ceil_div(Hq * Wq, 256), B), dim3(256), 0, st, feat_in, C, Hq * Wq,
-                         ss_in);
-    hipLaunchKernelGGL(patch_norm_kernel, dim3(ceil_div(Hqp * Wqp, 256), B), dim3(256), 0, st, ss_in_pre ? ss_in_pre : ss_in, Hq, Wq, patch,
-                       in_stride, Hqp, Wqp, 0, qden);
-    if ((rc = check_launch()) != C2M_OK) return rc;
-  }
+  if ((norm_input || use_filter) &&
+      (rc = launch_patch_norms(st, feat_in, ss_in_pre, ss_in, B, C, Hq, Wq, patch, in_stride, 0, qden)) != C2M_OK)
+    return rc;
   const float* invp = is_norm ? inv : nullptr;
   const float* qdp = norm_input ? qden : nullptr;
 
   if (fast) {
     int* row_eq = reinterpret_cast<int*>(wsb + ws.row_eq);
     int2* skip = reinterpret_cast<int2*>(wsb + ws.skip);
-    const c2m::corrf::Ws* fwsp = use_filter ? &ws.f : nullptr;
-    static const int dedup = [] {
-      const char* e = getenv("C2M_CORR_DEDUP");  // 0: score every ref row (measurement / debugging)
-      return (e && e[0] == '0') ? 0 : 1;
-    }();
-    if (C == 256)
-      return launch_corr_mfma<256>(st, feat_in, feat_ref, B, Hq, Wq, Hr, Wr, invp, qdp, row_eq, skip, dedup, max_idx,
-                                   max_val, fwsp, wsb, qden);
-    if (C == 128)
-      return launch_corr_mfma<128>(st, feat_in, feat_ref, B, Hq, Wq, Hr, Wr, invp, qdp, row_eq, skip, dedup, max_idx,
-                                   max_val, fwsp, wsb, qden);
-    return launch_corr_mfma<64>(st, feat_in, feat_ref, B, Hq, Wq, Hr, Wr, invp, qdp, row_eq, skip, dedup, max_idx,
-                                max_val, fwsp, wsb, qden);
+    with_constant<64, 128, 256>(C, [&](auto c) {
+      rc = launch_corr_mfma<decltype(c)::value>(st, feat_in, feat_ref, B, Hq, Wq, Hr, Wr, ws.nxt, invp, qdp, row_eq, skip, max_idx,
+                                                max_val, use_filter ? &ws.f : nullptr, wsb, qden);
+    });
+    return rc;
   }
+  const int Hqp = (Hq - patch) / in_stride + 1, Wqp = (Wq - patch) / in_stride + 1;
+  const int Hrp = (Hr - patch) / ref_stride + 1, Wrp = (Wr - patch) / ref_stride + 1;
   const size_t lds = sizeof(float) * (size_t)patch * patch * C;
   if (lds > 60 * 1024) return C2M_ERR_UNSUPPORTED;
   ProfileScope prof(C2M_KERNEL_CORR_GENERIC, st);

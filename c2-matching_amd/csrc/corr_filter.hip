@@ -34,20 +34,14 @@
 // 1.3 % more (profiles/r04_corr_band_histogram_lr160.json); measured |F - R| is 3.5e-7.
 #include "corr_filter.h"
 
-#include <stdlib.h>
-
-#include "c2m_common.h"
-
 namespace c2m {
 namespace corrf {
 
-constexpr int TQ = 16, TPQ = TQ - 2, WT = 32, NWAVE = 8, NTHR = NWAVE * 64, QPIX = TQ * TQ, SLAB = QPIX * WT, NIT = TPQ;
 constexpr float BAND_ALPHA = 8.4e-5f, BAND_BETA = 1.0e-6f, INV_CAP = 2.0f;
 constexpr float PIECE_SCALE = 16384.0f;                 // 2^14: both maps are split in this scaled domain
 constexpr float SCORE_UNSCALE = 3.725290298461914e-9f;  // 2^-28, folded into the candidate scales
 constexpr float F16_MIN_NORMAL = 6.103515625e-5f;   // 2^-14
 constexpr int SCAN_FLAG = 0x40000000;
-constexpr int SCAN_CAP = SCAN_ITEMS;           // work-list entries (whole-lane / whole-map re-scores); more: exact sweep
 constexpr int SCAN_CHUNKS = 32, SCAN_STRIPES = 64;
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -582,7 +576,7 @@ __global__ void __launch_bounds__(256) corr_resolve_kernel(const float* __restri
   auto defer = [&](int lane) __attribute__((always_inline)) {
     if (tap == 0) {
       const int slot = atomicAdd(&flags[1], 1);
-      if (slot < SCAN_CAP) items[slot] = ScanItem{q, lane, 0};
+      if (slot < SCAN_ITEMS) items[slot] = ScanItem{q, lane, 0};
       else flags[0] = 1;   // work list full: the exact sweep takes over
     }
     deferred = true;
@@ -619,7 +613,7 @@ __global__ void __launch_bounds__(256) corr_scan_kernel(const float* __restrict_
                                                          int Hr, int Wr, const float* __restrict__ inv,
                                                          const ScanItem* __restrict__ items, const int* __restrict__ flags,
                                                          unsigned long long* __restrict__ keys) {
-  const int count = min(flags[1], SCAN_CAP);
+  const int count = min(flags[1], SCAN_ITEMS);
   const int l = threadIdx.x & 63, grp = l / 9, tap = l - grp * 9;
   if (grp >= 7) return;
   const int g = (threadIdx.x >> 6) * 7 + grp;   // 0..27
@@ -644,7 +638,7 @@ __global__ void __launch_bounds__(256) corr_scan_finish_kernel(const ScanItem* _
                                                                 const unsigned long long* __restrict__ keys,
                                                                 const float* __restrict__ qden, int norm_input,
                                                                 int64_t* __restrict__ max_idx, float* __restrict__ max_val) {
-  const int count = min(flags[1], SCAN_CAP);
+  const int count = min(flags[1], SCAN_ITEMS);
   for (int it = blockIdx.x * 256 + threadIdx.x; it < count; it += gridDim.x * 256) {
     const long long q = items[it].q;
     float v;
@@ -656,22 +650,9 @@ __global__ void __launch_bounds__(256) corr_scan_finish_kernel(const ScanItem* _
   }
 }
 
-template <int C>
-static int launch_filter_c(hipStream_t st, const _Float16* qpl, const _Float16* rimg, int B, int Hq, int Wq, int Hr, int Wr,
-                           const float* sc, const float* band, const int2* skip, int* cnt, int* cand) {
-  const int tiles_y = ceil_div(Hq - 2, TPQ), tiles_x = ceil_div(Wq - 2, TPQ);
-  const size_t lds = sizeof(float) * (size_t)(3 * SLAB) + 2 * (size_t)C * 128;
-  static unsigned long long lds_set = 0;
-  auto kern = &corr_filter_kernel<C>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set)) return rc;
-  ProfileScope prof(C2M_KERNEL_CORR_FILTER, st);
-  hipLaunchKernelGGL(kern, dim3(B * tiles_y * tiles_x), dim3(NTHR), lds, st, qpl, rimg, Hq, Wq, Hr, Wr, tiles_y, tiles_x, sc, band,
-                     skip, cnt, cand);
-  return check_launch();
-}
-
-int launch(hipStream_t st, const float* fin, const float* fref, int B, int C, int Hq, int Wq, int Hr, int Wr, const float* inv,
-           const float* qden, int norm_input, int2* skip, char* wsbase, const Ws& ws, int64_t* max_idx, float* max_val) {
+int launch(hipStream_t st, const float* fin, const float* fref, int B, int C, int Hq, int Wq, int Hr, int Wr, int nxt,
+           const float* inv, const float* qden, int norm_input, int2* skip, char* wsbase, const Ws& ws, int64_t* max_idx,
+           float* max_val) {
   float* qn = reinterpret_cast<float*>(wsbase + ws.qn);
   float* rn = reinterpret_cast<float*>(wsbase + ws.rn);
   _Float16* qpl = reinterpret_cast<_Float16*>(wsbase + ws.qpl);
@@ -685,11 +666,9 @@ int launch(hipStream_t st, const float* fin, const float* fref, int B, int C, in
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(wsbase + ws.keys);
   ScanItem* items = reinterpret_cast<ScanItem*>(wsbase + ws.items);
   const int HWq = Hq * Wq, HWr = Hr * Wr, Hqp = Hq - 2, Wqp = Wq - 2, Hrp = Hr - 2, Wrp = Wr - 2;
-  const int nxt = ceil_div(Wrp, WP);
   const long long nqp = (long long)B * Hqp * Wqp, npix_r = (long long)B * HWr;
 
   int* maxcol = reinterpret_cast<int*>(wsbase + ws.maxcol);
-  static const int dead_tiles = [] { const char* e = getenv("C2M_CORR_DEAD_TILES"); return e ? atoi(e) : 1; }();   // (0: measurement)
   (void)hipMemsetAsync(flags, 0, 32, st);
   (void)hipMemsetAsync(maxcol, 0, sizeof(int) * (size_t)B, st);
   hipLaunchKernelGGL(to_nhwc_split_kernel, dim3(ceil_div(HWq, 64), C / 64, B), dim3(256), 0, st, fin, C, HWq, qn, qpl, flags);
@@ -698,13 +677,21 @@ int launch(hipStream_t st, const float* fin, const float* fref, int B, int C, in
   hipLaunchKernelGGL(pixel_eq_kernel, dim3((unsigned)((npix_r + 3) / 4)), dim3(256), 0, st, rn, C, Hr, Wr, npix_r, eq);
   hipLaunchKernelGGL(cand_scale_kernel, dim3(ceil_div(Hrp * Wrp, 256), B), dim3(256), 0, st, inv, eq, npix_r, Hr, Wr, Hrp, Wrp, sc,
                      flags, maxcol);
-  if (dead_tiles) hipLaunchKernelGGL(dead_tiles_kernel, dim3(ceil_div(B * nxt, 64)), dim3(64), 0, st, maxcol, nxt, B * nxt, Hr, skip);
+  hipLaunchKernelGGL(dead_tiles_kernel, dim3(ceil_div(B * nxt, 64)), dim3(64), 0, st, maxcol, nxt, B * nxt, Hr, skip);
   hipLaunchKernelGGL(band_kernel, dim3((unsigned)((nqp + 255) / 256)), dim3(256), 0, st, qden, nqp, band);
   int rc = check_launch();
   if (rc != C2M_OK) return rc;
-  if (C == 256) rc = launch_filter_c<256>(st, qpl, rimg, B, Hq, Wq, Hr, Wr, sc, band, skip, cnt, cand);
-  else if (C == 128) rc = launch_filter_c<128>(st, qpl, rimg, B, Hq, Wq, Hr, Wr, sc, band, skip, cnt, cand);
-  else rc = launch_filter_c<64>(st, qpl, rimg, B, Hq, Wq, Hr, Wr, sc, band, skip, cnt, cand);
+  {
+    const QueryTiles tiles = query_tiles(Hq, Wq);
+    ProfileScope prof(C2M_KERNEL_CORR_FILTER, st);
+    with_constant<64, 128, 256>(C, [&](auto c) {   // shapes_ok() admitted no other C
+      constexpr int CC = decltype(c)::value;
+      const size_t lds = sizeof(float) * (size_t)(3 * SLAB) + 2 * (size_t)CC * 128;
+      rc = launch_dynamic_lds<&corr_filter_kernel<CC>, NTHR>(dim3(B * tiles.y * tiles.x), lds, st, qpl, rimg, Hq, Wq, Hr, Wr,
+                                                             tiles.y, tiles.x, sc, band, skip, cnt, cand);
+    });
+    if (rc == C2M_OK) rc = check_launch();
+  }
   if (rc != C2M_OK) return rc;
   {
     ProfileScope prof(C2M_KERNEL_CORR_RESOLVE, st);

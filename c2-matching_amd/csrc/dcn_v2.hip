@@ -29,7 +29,6 @@
 // K orders: NCHW kernels k = (g * T + tap) * CPG + c_in_group (T = kh*kw, CPG = C/dg); channels-last forward
 // (tap, group, kk) with kk = 2t + hi <-> channel t + hi * CPG/2; offset/mask kernel: see weight_relayout_kernel.
 // Weights are re-laid out once per call (Wt[k][Co] forward, Wb[o][k] backward, Wh[k/8][Co][8] bf16).
-#include <type_traits>
 
 #include "c2m_common.h"
 
@@ -1411,23 +1410,6 @@ int relayout_geom(Geom& g, int C, int Co, int kh, int kw, int dg) {
   if (rc != C2M_OK) return rc;
   if (!use_nhwc(g)) return C2M_ERR_UNSUPPORTED;
   g.CoPad = copad_fwd(Co);
-  return C2M_OK;
-}
-
-// f(std::integral_constant<int, V>()) for the V of the list that equals v: turns a run-time choice into a template argument
-template <int... Vs, typename F>
-inline bool with_constant(int v, F&& f) {
-  return ((v == Vs && (f(std::integral_constant<int, Vs>()), true)) || ...);
-}
-
-// Launch a 256-thread kernel with `lds` bytes of dynamic LDS; above the 48 KiB a kernel gets by default its limit is raised
-// first (once per device: `lds_set` is this instantiation's, that is this kernel's, flag).
-template <auto Kernel, typename... Args>
-int launch_dynamic_lds(dim3 grid, size_t lds, hipStream_t st, Args... args) {
-  static unsigned long long lds_set = 0;
-  if (lds > 48 * 1024)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), lds, lds_set)) return rc;
-  hipLaunchKernelGGL(Kernel, grid, dim3(256), lds, st, args...);
   return C2M_OK;
 }
 

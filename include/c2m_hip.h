@@ -87,7 +87,7 @@ size_t c2m_feature_match_workspace_bytes_c(int B, int C, int Hq, int Wq, int Hr,
  * Diagnostics for the MFMA kernel's duplicate-row elimination: after c2m_feature_match_index_f32 the workspace holds,
  * at *byte_offset, int32 pairs [B][*x_tiles][2] = (from, to): ref pixel rows [from, to) of that (sample, x-tile) were
  * not swept because they repeat rows from-3 .. from-1 bit for bit (their patch rows can never win the lowest-index
- * tie rule of ref_map_util.py:74).  from == to: every row swept.  $C2M_CORR_DEDUP=0 disables the elimination.
+ * tie rule of ref_map_util.py:74).  from == to: every row swept.
  */
 int c2m_feature_match_skip_table(int B, int Hq, int Wq, int Hr, int Wr, size_t* byte_offset, int* x_tiles);
 

@@ -445,3 +445,85 @@ def test_prefilter_near_ties_are_resolved_exactly(env, dev):
         tab = ops.last_corr_filter_tables()
     assert np.array_equal(gi, oi) and np.array_equal(gv, ov)
     assert int(tab["flags"][0]) == 0 and float((tab["cnt"] >= 2).float().mean()) > 0.5   # the near-twins were both listed
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the host dispatch arms no other small case selects: every C with Wr % 4 == 0 (16-byte row DMA), and the dword DMA at
+# Wr % 4 == 0 behind a misaligned ref base
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def dma_cases(env):
+    """(fi, fr, {norm_input: (oracle idx, oracle val)}) per (C, Wr): one query tile against a 5-row ref of two (Wr = 32) or
+    three (Wr = 60) x-tiles, the last one ragged at two patch columns.  Computed once, read-only."""
+    _, oracle, synth = env
+    cases = {}
+    for C in (64, 128, 256):
+        for Wr in (32, 60):
+            fi = oracle.feature_normalize(synth.gaussish((C, 16, 16), 700 + C))
+            fr = oracle.feature_normalize(synth.gaussish((C, 5, Wr), 800 + C + Wr))
+            cases[C, Wr] = (fi, fr, {ni: oracle.feature_match_index(fi, fr, 3, 1, 1, True, ni) for ni in (False, True)})
+    return cases
+
+
+@pytest.mark.parametrize("misaligned", [False, True])
+@pytest.mark.parametrize("Wr", [32, 60])
+@pytest.mark.parametrize("C", [64, 128, 256])
+def test_row_dma_arms_at_every_channel_count(env, dev, dma_cases, C, Wr, misaligned):
+    """Wr % 4 == 0 with a 16-byte aligned ref selects corr_argmax_mfma_kernel<C, true>; the same map one float into a larger
+    buffer (base % 16 == 4) selects <C, false>.  Either way, with and without norm_input, from the exact sweep and from the
+    pre-filter path: the oracle's index map and values bit for bit, and the pre-filter produced its result itself."""
+    ops, _, _ = env
+    fi, fr, want = dma_cases[C, Wr]
+    q = _t(fi[None], dev)
+    if misaligned:
+        buf = torch.empty(fr.size + 4, dtype=torch.float32, device=dev)
+        r = buf[1:1 + fr.size].view(1, C, 5, Wr)
+        r.copy_(_t(fr[None], dev))
+        assert r.is_contiguous() and r.data_ptr() % 16 == 4
+    else:
+        r = _t(fr[None], dev)
+        assert r.data_ptr() % 16 == 0
+    for norm_input in (False, True):
+        oi, ov = want[norm_input]
+        got = {}
+        for mode in (0, 1):
+            with ops.corr_filter_mode(mode), ops.record_corr_skip_table():
+                idx, val = ops.feature_match_index_batched(q, r, 3, 1, 1, True, norm_input)
+                flags = ops.last_corr_filter_tables()["flags"]
+            got[mode] = (idx[0].cpu().numpy(), val[0].cpu().numpy())
+            assert np.array_equal(got[mode][0], oi) and np.array_equal(got[mode][1], ov), (mode, norm_input)
+            if mode == 1:
+                assert int(flags[0]) == 0, "the pre-filter fell back to the exact sweep on in-domain inputs"
+        assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
+@pytest.mark.parametrize("C", [64, 128, 96])
+def test_feature_normalize_bit_exact_small_channel_counts(env, dev, C):
+    """C = 64 / 128: the register kernels (test_feature_normalize_bit_exact covers 256); C = 96: the generic one."""
+    ops, oracle, synth = env
+    x = synth.gaussish((2, C, 7, 9), 60 + C)
+    x[1, :, 3, 4] = 0.0
+    got = ops.feature_normalize(_t(x, dev)).cpu().numpy()
+    assert np.array_equal(got, np.stack([oracle.feature_normalize(x[b]) for b in range(2)]))
+
+
+def test_filter_diagnostics_do_not_outlive_their_block(env, dev):
+    """`record_corr_skip_table()` resets both diagnostics slots when a block opens: the pre-filter tables an earlier block
+    recorded must not be readable in a later one.  Before the reset covered `filter` too, `last_corr_filter_tables()` returned
+    the previous block's tables until the new block's first launch (the first assertion inside the second block failed there; a
+    generic launch, which records nothing, then has to leave the slot empty as well)."""
+    import c2m_amd
+    ops, oracle, synth = env
+    fi = _t(oracle.feature_normalize(synth.gaussish((64, 8, 8), 91))[None], dev)
+    fr = _t(oracle.feature_normalize(synth.gaussish((64, 6, 7), 92))[None], dev)
+    with ops.record_corr_skip_table():
+        ops.feature_match_index_batched(fi, fr, 3, 1, 1, True, True)
+        assert ops.last_corr_filter_tables()["cnt"].shape == (1, 36)
+    with ops.record_corr_skip_table():
+        with pytest.raises(c2m_amd.C2MError):
+            ops.last_corr_filter_tables()
+        with pytest.raises(c2m_amd.C2MError):
+            ops.last_corr_skip_table()
+        ops.feature_match_index_batched(fi, fr, 3, 1, 1, True, True, force_generic=True)
+        with pytest.raises(c2m_amd.C2MError):
+            ops.last_corr_filter_tables()

@@ -139,7 +139,7 @@ def test_bench_flop_model_matches_kernel_tiling():
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "c2-matching_amd", "csrc", "corr_argmax.hip")).read()
+    src = open(os.path.join(root, "c2-matching_amd", "csrc", "corr_filter.h")).read()   # namespace corr: the one definition
     consts = {k: int(v) for k, v in re.findall(r"constexpr int (TQ|WT|WP|NWAVE) = (\d+);", src)}
     assert consts == {"TQ": 16, "WT": 32, "WP": 28, "NWAVE": 8}
     spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))

@@ -55,7 +55,8 @@ def test_no_measurement_scaffolding_in_the_shipped_library(tmp_path):
     if not os.path.exists(LIB):
         pytest.fail("libc2m_hip.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
     blob = open(LIB, "rb").read()
-    for name in (b"C2M_SPLIT_ABL", b"C2M_CONV_ABL", b"C2M_CORR_PF", b"C2M_SPLIT_TRACE", b"C2M_DCN_BWD_GROUPED"):
+    for name in (b"C2M_SPLIT_ABL", b"C2M_CONV_ABL", b"C2M_CORR_PF", b"C2M_SPLIT_TRACE", b"C2M_DCN_BWD_GROUPED",
+                 b"C2M_CORR_DEDUP", b"C2M_CORR_DEAD_TILES"):
         assert name not in blob, f"{name.decode()} is back in libc2m_hip.so"
     shutil.copy(LIB, tmp_path / "lib.so")
     subprocess.run([OBJDUMP, "--offloading", "lib.so"], cwd=tmp_path, check=True, capture_output=True)
