@@ -107,6 +107,9 @@ def _declare(L):
     L.c2m_contras_loss_backward_f32.argtypes = [_vp] + [_i] * 6 + [_vp] * 3 + [_i, _i] + [ctypes.c_float] * 3 + [_i] + [_vp] * 4 + [_sz]
     L.c2m_warp_perspective_u8.argtypes = [_vp] * 4 + [_i] * 3 + [_vp] * 3
     L.c2m_pil_bicubic_u8.argtypes = [_vp, _vp] + [_i] * 5 + [_vp] * 3 + [_i, _vp, _vp]
+    L.c2m_pil_bicubic2d_lds_bytes.restype = _sz
+    L.c2m_pil_bicubic2d_lds_bytes.argtypes = [_i] * 4
+    L.c2m_pil_bicubic2d_u8.argtypes = [_vp] * 3 + [_i] * 6 + ([_vp] * 3 + [_i]) * 2 + [_i, _i] + [_vp] * 3
 
 
 def lib():

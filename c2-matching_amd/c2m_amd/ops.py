@@ -1625,6 +1625,122 @@ def pil_bicubic_resize_u8(img_u8, out_h, out_w, as_float=False):
     return (x, xf) if as_float else x
 
 
+# ---- stage-3 batches: both resampling passes in one launch, flips / transpose on read (csrc/ref_pairs.hip) ---------------
+
+PIL2D_FLIP_H, PIL2D_FLIP_V, PIL2D_TRANSPOSE = 1, 2, 4      # the flag bits of a sample, applied in this order
+_PIL2D_TILE = 32                                           # C2M_PIL2D_TILE of include/c2m_hip.h
+_PIL2D_LDS_BUDGET = 64 * 1024                              # C2M_PIL2D_LDS_BUDGET
+
+Pil2dPlan = collections.namedtuple("Pil2dPlan", "win_h win_w Kh Kv lds_bytes fused")
+_pil2d_plans = {}
+
+
+def _pil2d_window(in_size, out_size):
+    """-> (the largest source window of any run of _PIL2D_TILE output pixels, K) of one axis' table."""
+    start, count, coeff = pil_bicubic_tables(in_size, out_size)
+    start, end = start.tolist(), (start + count).tolist()
+    win = max(max(end[t:t + _PIL2D_TILE]) - min(start[t:t + _PIL2D_TILE]) for t in range(0, len(start), _PIL2D_TILE))
+    return max(win, 1), int(coeff.shape[1])
+
+
+def pil_bicubic2d_plan(H, W, out_h, out_w):
+    """How pil_bicubic_resize2d_u8 runs a geometry: the source window (rows, columns) of one output tile, the tables' tap
+    counts, the LDS one workgroup needs, and `fused`: whether that fits the kernel's budget (else: two passes)."""
+    key = (int(H), int(W), int(out_h), int(out_w))
+    with _pil_tables_lock:
+        if key not in _pil2d_plans:
+            (win_h, Kv), (win_w, Kh) = _pil2d_window(key[0], key[2]), _pil2d_window(key[1], key[3])
+            lds = int(_lib.lib().c2m_pil_bicubic2d_lds_bytes(Kh, Kv, win_h, win_w))
+            _pil2d_plans[key] = Pil2dPlan(win_h, win_w, Kh, Kv, lds, 0 < lds <= _PIL2D_LDS_BUDGET)
+        return _pil2d_plans[key]
+
+
+def _pil2d_flags(flags, samples):
+    """flags (None, or one integer 0..7 per sample: a sequence, a numpy array or a CPU tensor) -> list of ints or None."""
+    if flags is None:
+        return None
+    if isinstance(flags, torch.Tensor):
+        if flags.is_cuda:
+            raise _lib.C2MError("flags stay on the host (they are checked there and uploaded with the launch)")
+        flags = flags.tolist()
+    try:
+        fl = [int(f) for f in flags]
+    except (TypeError, ValueError):
+        raise _lib.C2MError("flags must be one integer per sample")
+    if len(fl) != samples or any(f < 0 or f > 7 for f in fl):
+        raise _lib.C2MError(f"flags must be {samples} integers in 0..7 (bit 0 hflip, bit 1 vflip, bit 2 transpose)")
+    return fl
+
+
+def _orient_torch(x, flags):
+    """x [S, P, H, W], flags one int per sample -> the oriented batch by torch ops (sample by sample)."""
+    out = None
+    for b, f in enumerate(flags):
+        if not f:
+            continue
+        s = x[b]
+        dims = [d for d, bit in ((2, PIL2D_FLIP_H), (1, PIL2D_FLIP_V)) if f & bit]
+        if dims:
+            s = torch.flip(s, dims)
+        if f & PIL2D_TRANSPOSE:
+            s = s.transpose(1, 2)
+        if out is None:
+            out = x.clone()
+        out[b] = s
+    return x if out is None else out
+
+
+def pil_bicubic_resize2d_u8(img_u8, out_h, out_w, flags=None, as_float=False, oriented_float=False):
+    """pil_bicubic_resize_u8 in ONE launch, with each sample's orientation applied while its planes are read.
+
+    img_u8: uint8 [H, W], [P, H, W] (one sample) or [S, P, H, W] on the GPU.  flags: None, or one integer per sample on
+    the host: bit 0 horizontal flip, bit 1 vertical flip, bit 2 transpose (square planes only), applied in that order as
+    the reference's augment does.  -> uint8 [..., out_h, out_w], bit for bit pil_bicubic_resize_u8 of the oriented image
+    (Pillow's horizontal pass, uint8, vertical pass; an unchanged axis is skipped).  as_float adds float32 = uint8 / 255
+    of the result, oriented_float adds float32 = the oriented, unresized input / 255; the return value is the uint8
+    tensor alone or a tuple in that order.
+    A workgroup makes one 32 x 32 output tile from a source window held in LDS.  Where that window does not fit the
+    kernel's budget (pil_bicubic2d_plan(...).fused is False: down-scaling ratios above about 6) the same bits come from
+    torch flips and the two-pass operator."""
+    x = _dev_u8(img_u8, "img_u8")
+    if x.dim() not in (2, 3, 4) or x.numel() == 0:
+        raise _lib.C2MError("img_u8 must be a non-empty [H, W], [P, H, W] or [S, P, H, W] tensor")
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h <= 0 or out_w <= 0:
+        raise _lib.C2MError("out_h / out_w must be positive")
+    H, W = x.shape[-2:]
+    S = x.shape[0] if x.dim() == 4 else 1
+    N = x.numel() // (H * W)
+    fl = _pil2d_flags(flags, S)
+    if fl is not None and not any(fl):
+        fl = None
+    if fl is not None and H != W and any(f & PIL2D_TRANSPOSE for f in fl):
+        raise _lib.C2MError(f"a transpose flag needs square planes, got {H} x {W}")
+    if fl is None and not as_float and not oriented_float and (H, W) == (out_h, out_w):
+        return x.clone()
+    plan = pil_bicubic2d_plan(H, W, out_h, out_w)
+    with torch.cuda.device(x.device):
+        if plan.fused:
+            shape = tuple(x.shape[:-2]) + (out_h, out_w)
+            out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+            outf = torch.empty(shape, dtype=torch.float32, device=x.device) if as_float else None
+            orient = torch.empty(x.shape, dtype=torch.float32, device=x.device) if oriented_float else None
+            fdev = torch.tensor(fl, dtype=torch.uint8).to(x.device) if fl is not None else None
+            ht, vt = _pil_tables_on(W, out_w, x.device), _pil_tables_on(H, out_h, x.device)
+            _lib.check(_lib.lib().c2m_pil_bicubic2d_u8(
+                _stream(), x.data_ptr(), fdev.data_ptr() if fdev is not None else None, N, N // S, H, W, out_h, out_w,
+                ht[0].data_ptr(), ht[1].data_ptr(), ht[2].data_ptr(), plan.Kh, vt[0].data_ptr(), vt[1].data_ptr(),
+                vt[2].data_ptr(), plan.Kv, plan.win_h, plan.win_w, out.data_ptr(),
+                outf.data_ptr() if as_float else None, orient.data_ptr() if oriented_float else None), "c2m_pil_bicubic2d_u8")
+        else:
+            o = x if fl is None else _orient_torch(x.reshape(S, N // S, H, W), fl).reshape(x.shape)
+            out = pil_bicubic_resize_u8(o, out_h, out_w, as_float=as_float)
+            out, outf = out if as_float else (out, None)
+            orient = pil_bicubic_resize_u8(o, H, W, as_float=True)[1] if oriented_float else None
+    res = (out,) + ((outf,) if as_float else ()) + ((orient,) if oriented_float else ())
+    return res if len(res) > 1 else out
+
+
 def warp_perspective_u8(src_u8, M):
     """The reference's ``cv2.warpPerspective(img, H_inverse, (W, H))`` and its transformed-coordinate grid for a batch.
 

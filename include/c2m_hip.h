@@ -454,6 +454,32 @@ int c2m_warp_perspective_u8(c2m_stream_t stream, const uint8_t* src, const doubl
 int c2m_pil_bicubic_u8(c2m_stream_t stream, const uint8_t* src, int N, int H, int W, int vertical, int out_size,
                        const int* start, const int* count, const int* coeff, int K, uint8_t* dst_u8, float* dst_f32);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Stage-3 batches (ref_pairs.hip): both passes of Pillow's 8-bit bicubic resampler in ONE launch, the sample's flips and
+ * transpose applied while the source is read.  What mmsr/data/ref_cufed_dataset.py does per sample on the host (augment,
+ * then PIL.Image.resize down and back up) for a whole batch of uint8 planes.
+ *
+ * c2m_pil_bicubic2d_u8: src [N][H][W] uint8 planes; plane n belongs to sample n / planes_per_sample (N a multiple of it).
+ *   flags (DEVICE, one byte per sample, or NULL for none): bit 0 horizontal flip, bit 1 vertical flip, bit 2 transpose,
+ *   applied in that order; the transpose needs H == W (the caller checks; the kernel ignores the bit otherwise).  With O the
+ *   oriented plane:
+ *     dst_u8  [N][out_h][out_w] = the horizontal pass of c2m_pil_bicubic_u8 on O with the h_* table (W -> out_w), rounded
+ *       and clipped to uint8, then the vertical pass with the v_* table (H -> out_h): bit for bit the two calls.  An axis
+ *       that keeps its size takes the identity table (count 1, coefficient 2^22), which is Pillow skipping that pass.
+ *     dst_f32 (or NULL) the same pixels as fp32 p / 255;  orient_f32 (or NULL) [N][H][W] = O / 255 in fp32.
+ *   One workgroup makes one C2M_PIL2D_TILE x C2M_PIL2D_TILE output tile from LDS.  win_h / win_w: the largest source window
+ *   of any tile, max over tiles of (start + count of the tile's last row) - (start of its first row), per axis, computed by
+ *   the caller from its host copy of the tables.  c2m_pil_bicubic2d_lds_bytes gives the LDS one workgroup then needs; above
+ *   C2M_PIL2D_LDS_BUDGET the call returns C2M_ERR_UNSUPPORTED and the caller runs the two passes of c2m_pil_bicubic_u8.
+ */
+#define C2M_PIL2D_TILE 32
+#define C2M_PIL2D_LDS_BUDGET 65536
+size_t c2m_pil_bicubic2d_lds_bytes(int Kh, int Kv, int win_h, int win_w);
+int c2m_pil_bicubic2d_u8(c2m_stream_t stream, const uint8_t* src, const uint8_t* flags, int N, int planes_per_sample, int H,
+                         int W, int out_h, int out_w, const int* h_start, const int* h_count, const int* h_coeff, int Kh,
+                         const int* v_start, const int* v_count, const int* v_coeff, int Kv, int win_h, int win_w,
+                         uint8_t* dst_u8, float* dst_f32, float* orient_f32);
+
 #ifdef __cplusplus
 }
 #endif
