@@ -34,6 +34,12 @@ class Conv3x3Desc(ctypes.Structure):
                 ("out2_img_pitch", ctypes.c_longlong), ("range_flag", _vp), ("io_flags", ctypes.c_int)]
 
 
+class ImageSrc(ctypes.Structure):
+    """c2m_image_src of include/c2m_hip.h"""
+    _fields_ = [("ptr", _vp), ("pix_pitch", ctypes.c_longlong), ("row_pitch", ctypes.c_longlong),
+                ("plane_pitch", ctypes.c_longlong), ("img_pitch", ctypes.c_longlong)]
+
+
 class C2MError(RuntimeError):
     pass
 
@@ -110,6 +116,10 @@ def _declare(L):
     L.c2m_pil_bicubic2d_lds_bytes.restype = _sz
     L.c2m_pil_bicubic2d_lds_bytes.argtypes = [_i] * 4
     L.c2m_pil_bicubic2d_u8.argtypes = [_vp] * 3 + [_i] * 6 + ([_vp] * 3 + [_i]) * 2 + [_i, _i] + [_vp] * 3
+    L.c2m_val_metrics_tile.argtypes = [ctypes.POINTER(_i)] * 2
+    L.c2m_val_metrics_workspace_bytes.restype = _sz
+    L.c2m_val_metrics_workspace_bytes.argtypes = [_i] * 4
+    L.c2m_val_metrics_f32.argtypes = [_vp, ctypes.POINTER(ImageSrc), ctypes.POINTER(ImageSrc)] + [_i] * 7 + [_vp] * 4 + [_sz]
 
 
 def lib():

@@ -1772,3 +1772,104 @@ def warp_perspective_u8(src_u8, M):
                                                       dst_f32.data_ptr(), dst_u8.data_ptr(), coords.data_ptr()),
                    "c2m_warp_perspective_u8")
     return dst_f32, dst_u8, coords
+
+
+# ---- the end of validation: uint8 images and the metric sums in one pass (csrc/val_metrics.hip) ---------------------------
+
+def val_metrics_tile():
+    """(rows, columns) of SSIM-map positions one workgroup of the validation kernel makes, as the library reports them."""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().c2m_val_metrics_tile(ctypes.byref(th), ctypes.byref(tw)), "c2m_val_metrics_tile")
+    return th.value, tw.value
+
+
+def _image_src(t, name):
+    """fp32 [B,3,H,W] (or [3,H,W]) on the GPU -> (the 4-d tensor, its c2m_image_src).  Views are described, never copied."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.C2MError(f"{name} must be a tensor on the GPU (the HIP path has no CPU fallback)")
+    if t.dtype != torch.float32:
+        raise _lib.C2MError(f"{name} must be float32, got {t.dtype}")
+    t = t.detach()
+    if t.dim() == 3:
+        t = t[None]
+    if t.dim() != 4 or t.shape[1] != 3 or t.numel() == 0:
+        raise _lib.C2MError(f"{name} must be a non-empty [B,3,H,W] tensor, got {tuple(t.shape)}")
+    si, sp, sr, sx = t.stride()
+    return t, _lib.ImageSrc(t.data_ptr(), sx, sr, sp, si)
+
+
+def _image_order(images):
+    if images not in (None, 'bgr', 'rgb'):
+        raise _lib.C2MError(f"images must be None, 'bgr' or 'rgb', got {images!r}")
+    return int(images == 'rgb')
+
+
+def _valid_hw(valid_hw, H, W):
+    vh, vw = (H, W) if valid_hw is None else (int(valid_hw[0]), int(valid_hw[1]))
+    if not (0 < vh <= H and 0 < vw <= W):
+        raise _lib.C2MError(f"valid_hw {(vh, vw)} does not lie inside the {H} x {W} tensor")
+    return vh, vw
+
+
+def tensor_to_u8(t, order='bgr', valid_hw=None):
+    """fp32 RGB [B,3,H,W] (or [3,H,W]) on the GPU -> uint8 [B,vh,vw,3] (or [vh,vw,3]) = rint(clamp(t, 0, 1) * 255), half to
+    even, channels in `order` ('bgr': the reference's tensor2img; 'rgb': what Pillow writes), of the window valid_hw."""
+    if order not in ('bgr', 'rgb'):
+        raise _lib.C2MError(f"order must be 'bgr' or 'rgb', got {order!r}")
+    x, src = _image_src(t, "t")
+    B, _, H, W = x.shape
+    vh, vw = _valid_hw(valid_hw, H, W)
+    out = torch.empty((B, vh, vw, 3), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().c2m_val_metrics_f32(_stream(), ctypes.byref(src), None, B, H, W, vh, vw, 0, _image_order(order),
+                                                  out.data_ptr(), None, None, None, 0), "c2m_val_metrics_f32")
+    return out[0] if t.dim() == 3 else out
+
+
+def val_metrics_sums(sr, gt, crop_border=4, valid_hw=None, images=None):
+    """The kernel's own results: (sums float64 [B,3] = squared 8-bit difference, squared Y difference, SSIM_Y map, each
+    summed over the border-cropped window; sr_u8, gt_u8 uint8 [B,vh,vw,3] or None; (h, w) of the cropped window)."""
+    rgb = _image_order(images)
+    s, s_src = _image_src(sr, "sr")
+    g, g_src = _image_src(gt, "gt")
+    if s.shape[0] != g.shape[0] or s.device != g.device or (valid_hw is None and s.shape != g.shape):
+        raise _lib.C2MError(f"sr and gt must have one batch size and one device, and one shape unless valid_hw names their "
+                            f"common window; got {tuple(s.shape)} and {tuple(g.shape)}")
+    crop = int(crop_border)
+    if crop < 0:
+        raise _lib.C2MError("crop_border must be >= 0")
+    B, H, W = s.shape[0], min(s.shape[2], g.shape[2]), min(s.shape[3], g.shape[3])   # (only one of the two may be padded)
+    vh, vw = _valid_hw(valid_hw, H, W)
+    L = _lib.lib()
+    ws_bytes = int(L.c2m_val_metrics_workspace_bytes(B, vh, vw, crop))
+    sums = torch.empty((B, 3), dtype=torch.float64, device=s.device)
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=s.device)
+    s8 = torch.empty((B, vh, vw, 3), dtype=torch.uint8, device=s.device) if images else None
+    g8 = torch.empty((B, vh, vw, 3), dtype=torch.uint8, device=s.device) if images else None
+    with torch.cuda.device(s.device):
+        _lib.check(L.c2m_val_metrics_f32(_stream(), ctypes.byref(s_src), ctypes.byref(g_src), B, H, W, vh, vw, crop, rgb,
+                                         s8.data_ptr() if images else None, g8.data_ptr() if images else None,
+                                         sums.data_ptr(), ws.data_ptr(), ws_bytes), "c2m_val_metrics_f32")
+    return sums, s8, g8, (vh - 2 * crop, vw - 2 * crop)
+
+
+def _psnr_of_mse(mse):
+    # the expression of mmsr.utils.metrics.psnr
+    return torch.where(mse == 0, torch.full_like(mse, float('inf')), 20.0 * torch.log10(255.0 / torch.sqrt(mse)))
+
+
+def val_metrics(sr, gt, crop_border=4, valid_hw=None, images=None):
+    """PSNR, PSNR_Y and SSIM_Y of ``nondist_validation`` for a batch, in one pass over both tensors.
+
+    sr, gt: fp32 RGB [B,3,H,W] on the GPU; any view with a unit innermost stride is read in place.  valid_hw: the
+    un-padded (rows, columns) both are cropped to (default: everything); crop_border pixels are left out on every side of
+    that window.  -> dict of float64 tensors [B] 'psnr', 'psnr_y', 'ssim_y' with the definitions of
+    mmsr.utils.metrics.validation_metrics (inf where the mean squared error is 0).  images='bgr' / 'rgb' adds 'sr_u8' and
+    'gt_u8', uint8 [B,vh,vw,3] of the whole valid window in that channel order.  Nothing here waits for the device.
+    A cropped window with a side below 11 pixels (an empty SSIM map) raises C2MError."""
+    sums, s8, g8, (h, w) = val_metrics_sums(sr, gt, crop_border, valid_hw, images)
+    out = {'psnr': _psnr_of_mse(sums[:, 0] / (3 * h * w)), 'psnr_y': _psnr_of_mse(sums[:, 1] / (h * w)),
+           'ssim_y': sums[:, 2] / ((h - 10) * (w - 10))}
+    if images:
+        out['sr_u8'], out['gt_u8'] = s8, g8
+    return out

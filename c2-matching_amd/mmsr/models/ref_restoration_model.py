@@ -1,12 +1,13 @@
 """Stage-3 (MSE yaml) slice of the reference's ``RefRestorationModel`` (ref_restoration_model.py:21-43, 47-87,
 186-279): net construction through the registry, the four Adam parameter groups, ``feed_data`` / ``optimize_parameters``
-with the pixel loss / ``test``.  GAN, perceptual, texture losses, validation image I/O and LR schedulers are outside the
+with the pixel loss / ``test``.  GAN, perceptual, texture losses and LR schedulers are outside the
 hot path and are not provided here -- ``mmsr/train.py`` of the reference keeps using its own
 model file; this class is what bench/tests drive.
 
 Validation: ``nondist_validation`` computes PSNR / PSNR_Y / SSIM_Y with the reference's rules
-(ref_restoration_model.py:295-370) but on the device (mmsr/utils/metrics.py here: three scalars per image cross PCIe
-instead of two full images); ``dist_validation`` -- which in the reference calls a method that does not exist
+(ref_restoration_model.py:295-370) but on the device: one kernel reads SR and GT once and leaves three sums per image and,
+with ``save_img``, the uint8 image that is written as a PNG under the reference's path rules (c2m_amd.ops.val_metrics;
+``C2M_VAL_FUSED=0`` and CPU tensors take the torch composition of mmsr/utils/metrics.py); ``dist_validation`` -- which in the reference calls a method that does not exist
 (sr_model.py:160-162) -- shards the loader over the ranks and all-reduces the sums.
 
 MI355X addition -- ``train: {hip_graph: true}`` (single-process training): the whole training step (extractor +
@@ -16,8 +17,10 @@ captured once into a hipGraph (torch.cuda.CUDAGraph: static input buffers filled
 mode, two eager warm-up steps so that allocator, MIOpen find and lazy initialisation stay outside the capture) and
 replayed per ``optimize_parameters`` call -- same arithmetic, same kernels, one launch.
 """
+import collections
 import copy
 import logging
+import os
 
 import torch
 
@@ -26,6 +29,10 @@ from mmsr.models.base_model import BaseModel, unwrap
 from mmsr.utils import metrics
 
 logger = logging.getLogger('base')
+
+# C2M_VAL_FUSED (default 1): validation metrics and the saved image of fp32 tensors on the GPU by the one-pass kernel
+# (c2m_amd.ops.val_metrics); 0: the torch composition metrics.validation_metrics.  Read once, like the other switches.
+_VAL_FUSED = os.environ.get("C2M_VAL_FUSED", "1") != "0"
 
 
 class RefRestorationModel(BaseModel):
@@ -149,8 +156,54 @@ class RefRestorationModel(BaseModel):
         graph.replay()
 
     # ---------------------------------------------------------------- validation
-    def _validate_shard(self, dataloader, rank, world):
-        """-> float64 tensor [psnr_sum, psnr_y_sum, ssim_y_sum, count] over items idx % world == rank."""
+    def get_current_visuals(self):
+        """The reference's dict of host tensors (ref_restoration_model.py:281-287): 'img_in_lq', 'rlt' and, when fed, 'gt'."""
+        shown = [('img_in_lq', self.img_in_lq), ('rlt', self.output)] + ([('gt', self.gt)] if hasattr(self, 'gt') else [])
+        return collections.OrderedDict((k, t.detach().cpu()) for k, t in shown)
+
+    def _save_img_path(self, img_name, dataset_name, current_iter):
+        """Where the reference writes a validation image (ref_restoration_model.py:317-329): while training
+        <visualization>/<image>/<image>_<iter>.png, in a test run <visualization>/<dataset>/<image>_<name>[_<suffix>].png."""
+        root = (self.opt.get('path') or {}).get('visualization')
+        if not root:
+            raise ValueError("save_img needs opt['path']['visualization'] (the directory the images go to)")
+        if self.opt.get('is_train'):
+            return os.path.join(root, img_name, f'{img_name}_{current_iter}.png')
+        stem = f"{img_name}_{self.opt.get('name')}"
+        if self.opt.get('suffix'):
+            stem += f"_{self.opt['suffix']}"
+        return os.path.join(root, dataset_name, stem + '.png')
+
+    @staticmethod
+    def _img_names(val_data, idx, count):
+        """One name per item of the batch: the stem of its lq_path, or the loader index where the dict brings no paths."""
+        paths = val_data.get('lq_path')
+        if isinstance(paths, str):
+            paths = [paths]
+        names = [os.path.splitext(os.path.basename(p_))[0] for p_ in (paths or [])][:count]
+        for b in range(len(names), count):
+            names.append(str(idx) if count == 1 else f'{idx}_{b}')
+        return names
+
+    @staticmethod
+    def _write_png(rgb_u8, path):
+        """rgb_u8: uint8 [h, w, 3] host tensor, R G B."""
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise RuntimeError("save_img=True writes PNG files with Pillow, which is not installed "
+                               "(pip install pillow), or validate with save_img=False") from e
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        Image.fromarray(rgb_u8.contiguous().numpy(), 'RGB').save(path)
+
+    @staticmethod
+    def _fused_validation(sr, gt):
+        """The one-pass kernel takes fp32 tensors on the GPU (unless C2M_VAL_FUSED=0); everything else the torch composition."""
+        return bool(_VAL_FUSED and sr.is_cuda and gt.is_cuda and sr.dtype == torch.float32 and gt.dtype == torch.float32)
+
+    def _validate_shard(self, dataloader, rank, world, save=None):
+        """-> float64 tensor [psnr_sum, psnr_y_sum, ssim_y_sum, count] over items idx % world == rank.
+        save: None, or (dataset name, current_iter): the SR image of every item of the shard is written as a PNG."""
         crop = self.opt.get('crop_border')
         crop = self.opt.get('scale', 4) if crop is None else crop   # options.py:56-57
         sums = torch.zeros(4, dtype=torch.float64, device=self.device)
@@ -164,11 +217,24 @@ class RefRestorationModel(BaseModel):
                 self._eval_feed = False
             sr = self.test()
             gt = self.gt
+            valid = None
             if val_data.get('padding', False) is not False and bool(torch.as_tensor(val_data['padding']).any()):
-                oh, ow = (int(torch.as_tensor(v).flatten()[0]) for v in val_data['original_size'][:2])
-                sr = sr[..., :oh, :ow]          # the reference crops only the SR image (:311-315); shapes must then agree
-                gt = gt[..., :oh, :ow]
-            m = metrics.validation_metrics(sr, gt, crop_border=crop)
+                # the reference crops only the SR image (:311-315); shapes must then agree
+                valid = tuple(int(torch.as_tensor(v).flatten()[0]) for v in val_data['original_size'][:2])
+            if self._fused_validation(sr, gt):
+                # one pass over the padded tensors: the kernel reads the valid window only
+                m = metrics.validation_metrics_fused(sr, gt, crop_border=crop, valid_hw=valid, images='rgb' if save else None)
+                rgb = m['sr_u8'] if save else None
+            else:
+                if valid is not None:
+                    sr, gt = sr[..., :valid[0], :valid[1]], gt[..., :valid[0], :valid[1]]
+                with metrics.true_scalar_division():   # on the GPU too the composition divides by 255 as the reference does
+                    m = metrics.validation_metrics(sr, gt, crop_border=crop)
+                rgb = metrics.tensor2img_device(sr).flip(-1).to(torch.uint8) if save else None
+            if save:
+                rgb = rgb.cpu()
+                for b, img_name in enumerate(self._img_names(val_data, idx, rgb.shape[0])):
+                    self._write_png(rgb[b], self._save_img_path(img_name, save[0], save[1]))
             sums[0] += m['psnr'].sum()
             sums[1] += m['psnr_y'].sum()
             sums[2] += m['ssim_y'].sum()
@@ -188,21 +254,18 @@ class RefRestorationModel(BaseModel):
         return res
 
     def nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
-        if save_img:
-            raise NotImplementedError('image writing is outside the hot path (SURVEY.md 2.1)')
         name = getattr(getattr(dataloader, 'dataset', None), 'opt', {}).get('name', 'val')
-        return self._report(self._validate_shard(dataloader, 0, 1), name, current_iter, tb_logger)
+        sums = self._validate_shard(dataloader, 0, 1, save=(name, current_iter) if save_img else None)
+        return self._report(sums, name, current_iter, tb_logger)
 
     def dist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """Every rank validates its share of the loader; one all-reduce (RCCL on the GPU, gloo in the CPU tests) of four
-        float64 sums gives every rank the dataset averages."""
-        if save_img:
-            raise NotImplementedError('image writing is outside the hot path (SURVEY.md 2.1)')
+        float64 sums gives every rank the dataset averages.  With save_img every rank writes the images of its own share."""
         import torch.distributed as dist
         rank, world = dist.get_rank(), dist.get_world_size()
-        sums = self._validate_shard(dataloader, rank, world)
-        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
         name = getattr(getattr(dataloader, 'dataset', None), 'opt', {}).get('name', 'val')
+        sums = self._validate_shard(dataloader, rank, world, save=(name, current_iter) if save_img else None)
+        dist.all_reduce(sums, op=dist.ReduceOp.SUM)
         return self._report(sums, name, current_iter, tb_logger)
 
     def test(self):

@@ -10,6 +10,7 @@ import math
 
 import torch
 import torch.nn.functional as F
+from torch.overrides import TorchFunctionMode
 
 
 def tensor2img_device(t, min_max=(0, 1)):
@@ -91,5 +92,42 @@ def validation_metrics(sr, gt, crop_border=4):
             'ssim_y': ssim(sy[..., None], gy[..., None], crop_border)}
 
 
-__all__ = ['psnr', 'ssim', 'bgr2ycbcr', 'tensor2img_device', 'validation_metrics']
+class true_scalar_division(TorchFunctionMode):
+    """``with true_scalar_division():`` -- a tensor on the GPU divided by a Python number is divided, as on the CPU.
+
+    torch divides a CUDA tensor by a Python scalar by MULTIPLYING with the scalar's reciprocal, rounded to the tensor's type;
+    the CPU (and numpy, hence the reference) divides.  For ``s / 255.0`` in fp32 -- the first step of the Y channel in
+    ``validation_metrics`` -- the two differ by one ulp at 126 of the 256 8-bit values, which moves PSNR_Y by about 4e-7 dB
+    and SSIM_Y by about 1e-8 between the same function on the two devices.  Inside this context the scalar of such a division
+    becomes a 0-dim tensor on the tensor's device, which takes torch's true-division kernel: the composition then gives on the
+    GPU what it gives on the CPU (to float64 summation order).  CPU tensors and tensor / tensor divisions pass unchanged."""
+    _DIVS = ('div', 'div_', 'divide', 'divide_', 'true_divide', 'true_divide_', '__truediv__', '__itruediv__')
+
+    def __torch_function__(self, func, types, args=(), kwargs=None):
+        kwargs = kwargs or {}
+        if (getattr(func, '__name__', None) in self._DIVS and len(args) == 2 and isinstance(args[0], torch.Tensor)
+                and args[0].is_cuda and args[0].is_floating_point() and isinstance(args[1], (int, float))
+                and not isinstance(args[1], bool) and kwargs.get('rounding_mode') is None):
+            args = (args[0], torch.full((), float(args[1]), dtype=args[0].dtype, device=args[0].device))
+        return func(*args, **kwargs)
+
+
+def tensor2img_u8(t, order='bgr'):
+    """``tensor2img`` (util.py:107-162) on the device, uint8 included: [B,3,H,W] or [3,H,W] fp32 RGB tensor on the GPU ->
+    uint8 [.., H, W, 3] = ``tensor2img_device(t).to(uint8)``, channels in ``order`` ('bgr' as the reference, 'rgb' as
+    Pillow writes), by one hand-written kernel (c2m_amd.ops.tensor_to_u8)."""
+    from c2m_amd import ops
+    return ops.tensor_to_u8(t, order=order)
+
+
+def validation_metrics_fused(sr, gt, crop_border=4, valid_hw=None, images=None):
+    """``validation_metrics`` by one kernel that reads SR and GT once (c2m_amd.ops.val_metrics): the same dict, for fp32
+    tensors on the GPU.  valid_hw = (rows, columns): the un-padded window both tensors are cropped to first (padded tensors
+    are passed whole: no slicing copy); images='bgr' / 'rgb' adds 'sr_u8' / 'gt_u8', the uint8 images of that window."""
+    from c2m_amd import ops
+    return ops.val_metrics(sr, gt, crop_border=crop_border, valid_hw=valid_hw, images=images)
+
+
+__all__ = ['psnr', 'ssim', 'bgr2ycbcr', 'tensor2img_device', 'validation_metrics', 'tensor2img_u8', 'validation_metrics_fused',
+           'true_scalar_division']
 _ = math

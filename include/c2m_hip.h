@@ -480,6 +480,40 @@ int c2m_pil_bicubic2d_u8(c2m_stream_t stream, const uint8_t* src, const uint8_t*
                          const int* v_start, const int* v_count, const int* v_coeff, int Kv, int win_h, int win_w,
                          uint8_t* dst_u8, float* dst_f32, float* orient_f32);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The end of validation (val_metrics.hip): what the reference does per image on the host -- tensor2img
+ * (mmsr/utils/util.py:107-162), then psnr / bgr2ycbcr / ssim of mmsr/utils/metrics.py:34-168 on numpy arrays
+ * (ref_restoration_model.py:295-351) -- for a whole batch in one pass over SR and GT on the device.
+ *
+ * sr, gt: fp32 [B][3][H][W] RGB tensors described by HOST structs with element pitches, so that a view cropped with
+ *   [..., :oh, :ow] needs no copy; pix_pitch must be 1 (else C2M_ERR_UNSUPPORTED).  Only the valid window valid_h <= H,
+ *   valid_w <= W (the un-padded image) is read.  With v = rint(clamp(x, 0, 1) * 255.0f) in fp32, half to even:
+ *   sr_u8 / gt_u8 (each may be NULL) [B][valid_h][valid_w][3] uint8 = v, channels B G R (rgb_order == 0: tensor2img's order)
+ *     or R G B (rgb_order != 0), over the WHOLE valid window;
+ *   sums [B][3] float64 over the valid window less crop_border pixels on every side (h x w):
+ *     [0] sum over pixels and the 3 channels of (v_sr - v_gt)^2                                  PSNR    = mean over 3 h w
+ *     [1] sum of (Y_sr - Y_gt)^2, Y = ((24.966 B + 128.553 G + 65.481 R) / 255 + 16) / 255 * 255 in float64 of
+ *         (double)(v / 255.0f) * 255.0                                                            PSNR_Y  = mean over h w
+ *     [2] sum of the SSIM map of the Y images, 11 x 11 Gaussian window (sigma 1.5), 'valid' positions, C1 = 2.55^2,
+ *         C2 = 7.65^2, everything float64                                                         SSIM_Y  = mean over (h-10)(w-10)
+ *   min(valid_h, valid_w) - 2 crop_border < 11 gives C2M_ERR_UNSUPPORTED (the reference's mean of an empty map).
+ * One workgroup makes C2M_VAL_TILE_H x C2M_VAL_TILE_W positions of the SSIM map (c2m_val_metrics_tile reports the library's
+ * own values); per-workgroup sums go to `workspace` and a second launch adds them in a fixed order: no atomics, the same
+ * bits on every run.  gt == NULL: the image alone (sr_u8 required; gt_u8, sums NULL; no size limit, no workspace).
+ */
+typedef struct c2m_image_src {
+  const float* ptr;        /* sample 0, channel 0, pixel (0,0) */
+  long long pix_pitch;     /* elements between horizontally adjacent pixels: must be 1 */
+  long long row_pitch, plane_pitch, img_pitch;
+} c2m_image_src;
+#define C2M_VAL_TILE_H 16
+#define C2M_VAL_TILE_W 32
+int c2m_val_metrics_tile(int* tile_h, int* tile_w);
+size_t c2m_val_metrics_workspace_bytes(int B, int valid_h, int valid_w, int crop_border);   /* 0: rejected geometry */
+int c2m_val_metrics_f32(c2m_stream_t stream, const c2m_image_src* sr, const c2m_image_src* gt, int B, int H, int W,
+                        int valid_h, int valid_w, int crop_border, int rgb_order, uint8_t* sr_u8, uint8_t* gt_u8,
+                        double* sums, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
