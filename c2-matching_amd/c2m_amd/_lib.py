@@ -12,7 +12,7 @@ import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ($C2M_LIB: another build of the same library -- kernel A/B measurements; the product path is the in-tree build)
 LIB_PATH = os.environ.get("C2M_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libc2m_hip.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 _lib = None
@@ -63,8 +63,6 @@ def _declare(L):
     L.c2m_feature_match_index_pre_f32.restype = _i
     L.c2m_feature_normalize_ss_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp]
     L.c2m_feature_normalize_ss_f32.restype = _i
-    L.c2m_feature_match_set_filter.argtypes = [_i]
-    L.c2m_conv3x3_set_head_stores.argtypes = [_i]
     L.c2m_feature_match_filter_tables.argtypes = [_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)] * 3 + [ctypes.POINTER(ctypes.c_int)]
     L.c2m_build_pre_offsets_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]
     for name in ("c2m_dcn_v2_forward_workspace_bytes",):

@@ -75,10 +75,15 @@ def _pre_sumsq(t, B, HW):
     return ss
 
 
+_CORR_FORCE_GENERIC, _CORR_EXACT_SWEEP = 1, 2   # c2m_hip.h C2M_CORR_*: the `flags` word of the correlation entry points
+
+
 def feature_match_index_batched(feat_in, feat_ref, patch_size=3, input_stride=1, ref_stride=1, is_norm=True,
-                                norm_input=False, force_generic=False, return_skip=False):
+                                norm_input=False, force_generic=False, return_skip=False, exact_sweep=None):
     """Batched ref_map_util.feature_match_index: feat_in [B,C,Hq,Wq], feat_ref [B,C,Hr,Wr] ->
-    (max_idx int64 [B,Hqp,Wqp], max_val float32 [B,Hqp,Wqp]).  return_skip=True appends the MFMA kernel's duplicate-row
+    (max_idx int64 [B,Hqp,Wqp], max_val float32 [B,Hqp,Wqp]).  exact_sweep=True skips the f16 pre-filter and runs the exact
+    fp32 sweep only (identical results), False uses the pre-filter, None follows an open `corr_filter_mode` block (else the
+    pre-filter).  return_skip=True appends the MFMA kernel's duplicate-row
     table, int32 [B, x_tiles, 2] = (from, to) per (sample, ref x-tile) (c2m_feature_match_skip_table; diagnostics)."""
     fi, fr = _dev_f32(feat_in, "feat_in"), _dev_f32(feat_ref, "feat_ref")
     if fi.dim() != 4 or fr.dim() != 4 or fi.shape[:2] != fr.shape[:2] or fi.device != fr.device:
@@ -90,20 +95,22 @@ def feature_match_index_batched(feat_in, feat_ref, patch_size=3, input_stride=1,
         raise _lib.C2MError("feature maps smaller than the patch")
     Hqp, Wqp = (Hq - p) // si + 1, (Wq - p) // si + 1
     L = _lib.lib()
+    if exact_sweep is None:
+        exact_sweep = _corr_exact_sweep   # (read here, on the launching thread: corr_filter_mode)
+    flags = (_CORR_FORCE_GENERIC if force_generic else 0) | (_CORR_EXACT_SWEEP if exact_sweep else 0)
     with torch.cuda.device(fi.device):
         nbytes = L.c2m_feature_match_workspace_bytes_c(B, C, Hq, Wq, Hr, Wr)   # (sized by the maps' channels: ADVICE r4)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=fi.device)
         idx = torch.empty((B, Hqp, Wqp), dtype=torch.int64, device=fi.device)
         val = torch.empty((B, Hqp, Wqp), dtype=torch.float32, device=fi.device)
         ss_i, ss_r = _pre_sumsq(feat_in, B, Hq * Wq), _pre_sumsq(feat_ref, B, Hr * Wr)
-        with _apply_switch("filter"):
-            _lib.check(L.c2m_feature_match_index_pre_f32(_stream(), fi.data_ptr(), fr.data_ptr(), B, C, Hq, Wq, Hr, Wr, p, si,
-                                                         sr, int(bool(is_norm)), int(bool(norm_input)), int(bool(force_generic)),
-                                                         idx.data_ptr(), val.data_ptr(), ws.data_ptr(), nbytes,
-                                                         ss_i.data_ptr() if ss_i is not None else None,
-                                                         ss_r.data_ptr() if ss_r is not None else None),
-                       "c2m_feature_match_index_pre_f32")
-        mfma = (not force_generic) and p == 3 and si == 1 and sr == 1 and C in (64, 128, 256)   # restates mfma_channels() of csrc/corr_filter.h
+        _lib.check(L.c2m_feature_match_index_pre_f32(_stream(), fi.data_ptr(), fr.data_ptr(), B, C, Hq, Wq, Hr, Wr, p, si,
+                                                     sr, int(bool(is_norm)), int(bool(norm_input)), flags,
+                                                     idx.data_ptr(), val.data_ptr(), ws.data_ptr(), nbytes,
+                                                     ss_i.data_ptr() if ss_i is not None else None,
+                                                     ss_r.data_ptr() if ss_r is not None else None),
+                   "c2m_feature_match_index_pre_f32")
+        mfma = not (flags & _CORR_FORCE_GENERIC) and p == 3 and si == 1 and sr == 1 and C in (64, 128, 256)   # restates mfma_channels() of csrc/corr_filter.h
         if return_skip or _corr_diag.enabled:
             # diagnostics only (bench.py's swept-row count, the dedup tests): the duplicate-row table exists only when the
             # MFMA kernel ran; nothing is kept otherwise, so the workspace dies with the call and no module state is
@@ -169,68 +176,28 @@ def last_corr_filter_tables():
     return _corr_diag.filter
 
 
-# The library's two A/B switches (c2m_feature_match_set_filter, c2m_conv3x3_set_head_stores) are thread_local: a launch sees the
-# CALLING thread's setting.  The context managers below therefore also record the mode process-wide, and the op wrappers
-# re-apply it on whichever thread launches (under nn.DataParallel the replicas launch from worker threads, where a
-# `with ops.corr_filter_mode(0):` of the main thread used to have no effect -- an A/B pass would have measured the default path
-# without noticing).  Nesting / concurrent use from several threads with DIFFERENT modes is not supported (last writer wins).
-_switch_override = {"filter": None, "head": None}
+_corr_exact_sweep = False   # what `exact_sweep=None` means; corr_filter_mode saves, sets and restores it
 
 
-class _apply_switch:
-    """Re-apply a recorded process-wide override to this thread's C-ABI switch for the duration of one launch."""
-
-    def __init__(self, which):
-        self.which = which
-        self.mode = _switch_override[which]
-
-    def _set(self, mode):
-        L = _lib.lib()
-        fn = L.c2m_feature_match_set_filter if self.which == "filter" else L.c2m_conv3x3_set_head_stores
-        _lib.check(fn(mode), "c2m set switch")
-
-    def __enter__(self):
-        if self.mode is not None:
-            self._set(self.mode)
-        return self
-
-    def __exit__(self, *exc):
-        if self.mode is not None:
-            self._set(-1)
-        return False
-
-
-class _switch_mode:
-    """Base of the two A/B context managers: records the mode process-wide while the block is open (see above)."""
-    which = None
+class corr_filter_mode:
+    """`with ops.corr_filter_mode(0): ...` -- exact fp32 sweep only; (1): pre-filter + exact re-score (default); results are
+    identical (C2M_CORR_EXACT_SWEEP).  The default of feature_match_index_batched's `exact_sweep` for every thread's launches
+    through this module while the block is open (measurement / tests); an explicit `exact_sweep=` wins."""
 
     def __init__(self, mode):
         self.mode = int(mode)
         if self.mode not in (0, 1):
-            raise _lib.C2MError(f"{type(self).__name__}: 0 or 1")
+            raise _lib.C2MError("corr_filter_mode: 0 or 1")
 
     def __enter__(self):
-        self.prev = _switch_override[self.which]
-        _switch_override[self.which] = self.mode
+        global _corr_exact_sweep
+        self.prev, _corr_exact_sweep = _corr_exact_sweep, self.mode == 0
         return self
 
     def __exit__(self, *exc):
-        _switch_override[self.which] = self.prev
+        global _corr_exact_sweep
+        _corr_exact_sweep = self.prev
         return False
-
-
-class corr_filter_mode(_switch_mode):
-    """`with ops.corr_filter_mode(0): ...` -- exact fp32 sweep only; (1): pre-filter + exact re-score (default); results are
-    identical (c2m_feature_match_set_filter).  Applies to every thread's launches through this module while the block is open
-    (measurement / tests)."""
-    which = "filter"
-
-
-class head_store_mode(_switch_mode):
-    """`with ops.head_store_mode(0): ...` -- the DCN head epilogue's dword planar stores; (1): 16-byte stores through the quad
-    transpose + flow window (default where W % 4 == 0); identical results (c2m_conv3x3_set_head_stores).  Applies to every
-    thread's launches through this module while the block is open."""
-    which = "head"
 
 
 def last_corr_skip_table():
@@ -582,8 +549,6 @@ def empty_nhwc(B, C, H, W, device, dtype=torch.float32):
     return torch.empty((B, C, H, W), dtype=dtype, device=device, memory_format=torch.channels_last)
 
 
-_WINO = os.environ.get("C2M_CONV_WINO", "1") != "0"
-_WINO4 = os.environ.get("C2M_CONV_WINO4", "1") != "0"
 # C2M_CONV_SPLIT: "all" (default) -- every convolution the split-bf16 kernel supports runs on it (csrc/conv3x3_split.hip:
 # fp32-accurate, 6 bf16 MFMAs per fp32 product sum), the extractor towers that feed the index search included (measured on
 # configs[2]: 1 near-tie flip of 24 964 queries against the CPU chain, 2 with the fp32-MFMA kernels); "1" -- only calls
@@ -729,13 +694,13 @@ def f16_range_guard(owner, fn, device):
 
 def _wino_ok(srcs, weight, out_mode, W):
     """Winograd F(2,3)-along-x kernel: channels-last output, 64-wide cout tiles, whole 32-pixel tiles along x."""
-    return (_WINO and out_mode in ("nhwc", "nhwc_pool2") and weight.shape[0] % 64 == 0 and W % 32 == 0 and
+    return (out_mode in ("nhwc", "nhwc_pool2") and weight.shape[0] % 64 == 0 and W % 32 == 0 and
             all(s.shape[1] % 16 == 0 for s in srcs) and sum(s.shape[1] for s in srcs) == weight.shape[1])
 
 
 def _wino4_ok(srcs, weight, out_mode, W):
     """Winograd F(4,3)-along-x kernel: as F(2,3) but plain channels-last output and whole 64-pixel tiles along x."""
-    return _WINO4 and W % 64 == 0 and out_mode == "nhwc" and _wino_ok(srcs, weight, out_mode, W)
+    return W % 64 == 0 and out_mode == "nhwc" and _wino_ok(srcs, weight, out_mode, W)
 
 
 def bf16_autocast():
@@ -1070,12 +1035,15 @@ def index_to_flow(max_idx):
     return flow
 
 
-def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, abs_sum=None, algo=None):
+def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, abs_sum=None, algo=None, dword_stores=False):
     """The DCN offset/mask head (conv_offset_mask of DCN_sep_pre_multi_offset, dcn_v2.py:229-245) fused with the
     pre-offset construction: -> (offset [B,2*dg*9,H,W], mask [B,dg*9,H,W]) planar, ready for dcn_v2_forward.
     flow: index_to_flow(max_idx) of the matched LR features (or None: no pre-offset); scale = H / h (1, 2, 4).
     The head's channels are computed in slices of 64-channel tiles + one 32-wide remainder (216 = 192 + 24) so that
-    no padded tile is multiplied."""
+    no padded tile is multiplied.
+    dword_stores: split kernels: this call's epilogue stores one dword per lane and loads the flow per (4 channels, pixel)
+    instead of the 16-byte quad-transposed stores + register flow window that maps with W % 4 == 0 take (c2m_hip.h
+    C2M_IO_DWORD_STORES: same bits, the other instruction sequence; tests, measurement)."""
     srcs = _as_list(srcs)
     B, _, H, W = srcs[0].shape
     Cin = sum(s.shape[1] for s in srcs)
@@ -1096,7 +1064,9 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
     slices = [(0, Cout)] if (split == 0 or Cout - split > 32 or split == Cout) else [(0, split), (split, Cout)]
     use_split = algo in ("split", "bf16", "split16") or (algo is None and _SPLIT != "0" and all(s_.shape[1] % 16 == 0 for s_ in srcs))
     split_kind = _split_kind(algo)
-    wino = _WINO and algo is None and W % 32 == 0 and all(s_.shape[1] % 16 == 0 for s_ in srcs)
+    wino = algo is None and W % 32 == 0 and all(s_.shape[1] % 16 == 0 for s_ in srcs)
+    if dword_stores and not use_split:   # every slice's kind is then K_WINO / K_DIRECT, not one of _SPLIT_KINDS
+        raise _lib.C2MError("conv3x3_dcn_head: dword_stores selects a store path of the split kernels' epilogue")
     for (c0, c1) in slices:
         # split-bf16 kernel (any shape); else 64-channel-tileable slices on whole 32-pixel tiles take the Winograd F(2,3)
         # kernel (1.5x fewer matrix instructions), the rest the direct kernel
@@ -1111,8 +1081,9 @@ def conv3x3_dcn_head(srcs, weight, bias, deformable_groups, flow=None, scale=1, 
             d.flow, d.fh, d.fw = flow.data_ptr(), flow.shape[1], flow.shape[2]
         if abs_sum is not None:
             d.abs_sum = abs_sum.data_ptr()
-        with _apply_switch("head"):
-            _launch_conv(d, dev, kind, "dcn_head_")
+        if dword_stores:
+            d.io_flags = 16
+        _launch_conv(d, dev, kind, "dcn_head_")
     return offset, mask
 
 
@@ -1189,8 +1160,6 @@ def refresh_weight_caches(module_or_params=None, all_kinds=False):
     this once per forward: in-place writes through ``param.data`` do not bump the version counter the caches are keyed
     on, so without it such an update would keep computing with the old weights.  Returns the number of
     images rebuilt.  No host synchronisation."""
-    if os.environ.get("C2M_WEIGHT_REFRESH", "1") == "0":   # measurement only: what the per-forward refresh costs
-        return 0
     ids = None
     if module_or_params is not None:
         params = module_or_params.parameters() if hasattr(module_or_params, "parameters") else module_or_params

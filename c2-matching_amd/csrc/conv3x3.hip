@@ -1436,7 +1436,6 @@ namespace conv {   // conv3x3_split.hip
 size_t split_relayout_bytes(int Cin, int Cout, int np);
 int split_relayout(hipStream_t st, const float* weight, int Cin, int Cout, int np, void* wr, int dgrad);
 int launch_split(hipStream_t st, Params p, int np);
-int set_head_stores(int mode);
 int split_relayout_multi(hipStream_t st, const long long* jobs, int njobs, long long nblocks, int any_f16);
 }  // namespace conv
 }  // namespace c2m
@@ -1553,8 +1552,6 @@ extern "C" int c2m_index_to_flow_f32(c2m_stream_t stream, const int64_t* max_idx
   return check_launch();
 }
 
-extern "C" int c2m_conv3x3_set_head_stores(int mode) { return conv::set_head_stores(mode); }
-
 extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d) {
   if (!d || !d->wr || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->nsrc < 1 ||
       d->nsrc > 2 || !d->src[0].ptr || (d->nsrc == 2 && !d->src[1].ptr))
@@ -1619,8 +1616,8 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   p.out2_img_pitch = d->out2_img_pitch;
   p.range_flag = d->range_flag;
   p.io_flags = d->io_flags;
-  if (d->io_flags & C2M_IO_DWORD_STORES) {   // per-call reference store path of the split kernels' PixelShuffle / planar epilogues
-    if (!splitk || (d->out_mode != 1 && d->out_mode != 2) || (d->io_flags & ~C2M_IO_DWORD_STORES)) return C2M_ERR_UNSUPPORTED;
+  if (d->io_flags & C2M_IO_DWORD_STORES) {   // per-call reference store path of the split kernels' PixelShuffle / planar / DCN-head epilogues
+    if (!splitk || d->out_mode < 1 || d->out_mode > 3 || (d->io_flags & ~C2M_IO_DWORD_STORES)) return C2M_ERR_UNSUPPORTED;
   } else if (d->io_flags != 0) {
     if (d->algo != C2M_CONV_BF16 || d->out_mode != 0 || (d->io_flags & ~15)) return C2M_ERR_UNSUPPORTED;
     if ((d->io_flags & C2M_IO_SRC_BF16) && (d->nsrc != 1 || d->src[0].pix_pitch % 8 != 0 || d->src[0].row_pitch % 8 != 0 || d->src[0].img_pitch % 8 != 0))

@@ -750,7 +750,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_split_kernel(Params p) {
     if constexpr (MODE == 3 || MODE == 5) {
       float asum = 0.0f;
       const HeadOut ho = head_out(p, b);
-      // MODE 5 (W % 4 == 0; $C2M_HEAD_QUAD=0 keeps MODE 3): 16-byte planar stores after a 4 x 4 transpose inside the lane
+      // MODE 5 (W % 4 == 0; C2M_IO_DWORD_STORES keeps MODE 3): 16-byte planar stores after a 4 x 4 transpose inside the lane
       // quads, pre-offsets from a per-row flow window held in registers (conv3x3_shared.h)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
@@ -1061,8 +1061,6 @@ int split_relayout_multi(hipStream_t st, const long long* jobs, int njobs, long 
   return check_launch();
 }
 
-thread_local int g_head_stores = -1;   // c2m_conv3x3_set_head_stores
-
 // One flavour's kernels: [MT - 1][MODE], MODE = Params::out_mode 0 .. 4, 5 = the DCN head (3) with 16-byte quad stores; each
 // entry point with its ensure_dynamic_lds flag.
 template <int NP>
@@ -1077,11 +1075,7 @@ static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid, int MT)
   // planes (x2 when pipelined), weight ring (3 / 2 slots), dummy, bias
   size_t ldsb = (size_t)((NP != 3 ? 2 : 1) * split::npx_of(NP) * 2 * split::HALFB) + (NP != 3 ? 3 : 2) * (size_t)(3 * split::npw_of(NP) * MT * 1024) + 1024 + 256;
   int mode = p.out_mode;
-  if (mode == 3) {
-    static const int env_quad = [] { const char* e = getenv("C2M_HEAD_QUAD"); return e ? atoi(e) : 1; }();
-    const int head_quad = g_head_stores >= 0 ? g_head_stores : env_quad;
-    if (head_quad != 0 && p.W % 4 == 0) mode = 5;
-  }
+  if (mode == 3 && p.W % 4 == 0 && !(p.io_flags & C2M_IO_DWORD_STORES)) mode = 5;
   Kernel* k = &kernels[MT - 1][mode];
   if constexpr (NP == 1) {
     if (p.io_flags & C2M_IO_SRC_BF16) {   // bf16 source: three 12 KiB plane buffers filled by LDS-DMA
@@ -1108,12 +1102,6 @@ int launch_split(hipStream_t st, Params p, int np) {
   const int rc = np == 3 ? launch_split_mode<3>(st, p, grid, MT) : np == 2 ? launch_split_mode<2>(st, p, grid, MT) : launch_split_mode<1>(st, p, grid, MT);
   if (rc != C2M_OK) return rc;
   return check_launch();
-}
-
-int set_head_stores(int mode) {
-  if (mode < -1 || mode > 1) return C2M_ERR_INVALID_ARG;
-  g_head_stores = mode;
-  return C2M_OK;
 }
 
 }  // namespace conv

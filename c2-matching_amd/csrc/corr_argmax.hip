@@ -595,16 +595,6 @@ int launch_corr_mfma(hipStream_t st, const float* fin, const float* fref, int B,
 }
 }  // namespace
 
-namespace {
-thread_local int g_filter_mode = -1;   // -1: $C2M_CORR_FILTER (default on), 0 / 1: forced by c2m_feature_match_set_filter
-}
-
-extern "C" int c2m_feature_match_set_filter(int mode) {
-  if (mode < -1 || mode > 1) return C2M_ERR_INVALID_ARG;
-  g_filter_mode = mode;
-  return C2M_OK;
-}
-
 extern "C" int c2m_feature_match_filter_tables(int B, int Hq, int Wq, int Hr, int Wr, size_t* cnt_offset, size_t* cand_offset,
                                                size_t* flags_offset, int* slots) {
   if (B <= 0 || Hq <= 0 || Wq <= 0 || Hr <= 0 || Wr <= 0 || !cnt_offset || !cand_offset || !flags_offset || !slots)
@@ -640,20 +630,21 @@ extern "C" int c2m_feature_match_skip_table(int B, int Hq, int Wq, int Hr, int W
 
 extern "C" int c2m_feature_match_index_f32(c2m_stream_t stream, const float* feat_in, const float* feat_ref, int B,
                                            int C, int Hq, int Wq, int Hr, int Wr, int patch, int in_stride,
-                                           int ref_stride, int is_norm, int norm_input, int force_generic,
+                                           int ref_stride, int is_norm, int norm_input, int flags,
                                            int64_t* max_idx, float* max_val, void* workspace,
                                            size_t workspace_bytes) {
   return c2m_feature_match_index_pre_f32(stream, feat_in, feat_ref, B, C, Hq, Wq, Hr, Wr, patch, in_stride, ref_stride, is_norm,
-                                         norm_input, force_generic, max_idx, max_val, workspace, workspace_bytes, nullptr, nullptr);
+                                         norm_input, flags, max_idx, max_val, workspace, workspace_bytes, nullptr, nullptr);
 }
 
 extern "C" int c2m_feature_match_index_pre_f32(c2m_stream_t stream, const float* feat_in, const float* feat_ref, int B,
                                                int C, int Hq, int Wq, int Hr, int Wr, int patch, int in_stride,
-                                               int ref_stride, int is_norm, int norm_input, int force_generic,
+                                               int ref_stride, int is_norm, int norm_input, int flags,
                                                int64_t* max_idx, float* max_val, void* workspace,
                                                size_t workspace_bytes, const float* ss_in_pre, const float* ss_ref_pre) {
   if (!feat_in || !feat_ref || !max_idx || !max_val) return C2M_ERR_INVALID_ARG;
   if (B <= 0 || C <= 0 || patch <= 0 || in_stride <= 0 || ref_stride <= 0) return C2M_ERR_INVALID_ARG;
+  if (flags & ~(C2M_CORR_FORCE_GENERIC | C2M_CORR_EXACT_SWEEP)) return C2M_ERR_INVALID_ARG;
   if (Hq < patch || Wq < patch || Hr < patch || Wr < patch) return C2M_ERR_INVALID_ARG;
   const CorrWs ws = corr_ws(B, Hq, Wq, Hr, Wr, filter_channels(C));   // (<= what either size query returns)
   if (!workspace || workspace_bytes < ws.total) return C2M_ERR_WORKSPACE;
@@ -667,15 +658,10 @@ extern "C" int c2m_feature_match_index_pre_f32(c2m_stream_t stream, const float*
   int rc = C2M_OK;
   if (is_norm && (rc = launch_patch_norms(st, feat_ref, ss_ref_pre, ss_ref, B, C, Hr, Wr, patch, ref_stride, 1, inv)) != C2M_OK)
     return rc;
-  const bool fast = !force_generic && patch == 3 && in_stride == 1 && ref_stride == 1 && c2m::corr::mfma_channels(C);
+  const bool fast = !(flags & C2M_CORR_FORCE_GENERIC) && patch == 3 && in_stride == 1 && ref_stride == 1 && c2m::corr::mfma_channels(C);
   // The pre-filter path (corr_filter.hip): 3/16 of the matrix time, same results.  It needs the ref-patch normalisation
-  // (its error bound is relative to |r|) and shapes its 16-bit candidate codes cover.  $C2M_CORR_FILTER=0: exact sweep only.
-  static const int filter_env = [] {
-    const char* e = getenv("C2M_CORR_FILTER");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  const int filter_on = g_filter_mode < 0 ? filter_env : g_filter_mode;
-  const bool use_filter = fast && filter_on && is_norm && c2m::corrf::shapes_ok(B, C, Hq, Wq, Hr, Wr);
+  // (its error bound is relative to |r|) and shapes its 16-bit candidate codes cover.  C2M_CORR_EXACT_SWEEP: exact sweep only.
+  const bool use_filter = fast && !(flags & C2M_CORR_EXACT_SWEEP) && is_norm && c2m::corrf::shapes_ok(B, C, Hq, Wq, Hr, Wr);
   if ((norm_input || use_filter) &&
       (rc = launch_patch_norms(st, feat_in, ss_in_pre, ss_in, B, C, Hq, Wq, patch, in_stride, 0, qden)) != C2M_OK)
     return rc;

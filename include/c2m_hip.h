@@ -43,7 +43,7 @@ typedef enum c2m_status {
   C2M_ERR_NO_DEVICE = 5      /* no gfx950 device visible to the HIP runtime */
 } c2m_status;
 
-int c2m_abi_version(void);                 /* bumped on any signature change; currently 4 (v4: unserved residual-block entry points removed) */
+int c2m_abi_version(void);                 /* bumped on any signature change; currently 5 (v5: the correlation takes a flags word, the two A/B setters removed) */
 const char* c2m_status_string(int status); /* static string, never NULL */
 const char* c2m_last_hip_error(void);      /* hipGetErrorString of the last failing HIP call on this thread */
 int c2m_device_arch(char* buf, int buflen);/* gcnArchName of the current device, e.g. "gfx950:sramecc+:xnack-" */
@@ -92,29 +92,6 @@ size_t c2m_feature_match_workspace_bytes_c(int B, int C, int Hq, int Wq, int Hr,
 int c2m_feature_match_skip_table(int B, int Hq, int Wq, int Hr, int Wr, size_t* byte_offset, int* x_tiles);
 
 /*
- * The MFMA path of c2m_feature_match_index_f32 has two implementations with identical results (indices AND values):
- *   exact sweep   every (query, ref patch) score on the fp32 matrix pipe (corr_argmax.hip);
- *   pre-filter    the same sweep on the f16 matrix pipe (two pieces per operand, three products: 3/16 of the matrix time)
- *                 keeps, per query, every candidate whose filter score lies within a RIGOROUS error band of the best one
- *                 (8.4e-5 |query patch| + 1e-6); the listed candidates are then re-scored with the oracle's exact fp32
- *                 chain and the first maximum taken (corr_filter.hip).  Needs is_norm, |x| < 3.99 everywhere and ref patch
- *                 norms >= 0.5 (channel-normalised features satisfy all three); anything else falls back to the exact
- *                 sweep on the device, without a host round trip.
- * mode: 1 pre-filter (default), 0 exact sweep only, -1 follow $C2M_CORR_FILTER (unset = 1).  Per CALLING THREAD (thread_local: a
- * DataParallel replica thread or another stream's host thread never sees a test's setting); measurement and tests.
- */
-int c2m_feature_match_set_filter(int mode);
-
-/*
- * The DCN offset/mask head epilogue (C2M_OUT_DCN_HEAD) of the split kernels has two store paths with identical results:
- *   1 (default, maps with W % 4 == 0)  16-byte planar stores after a 4 x 4 register transpose inside lane quads, pre-offsets
- *                                      from a per-row flow window held in registers (ds_bpermute look-ups);
- *   0                                  dword planar stores, one 8-byte flow load per (4 channels, pixel).
- * mode: 1 / 0, -1 follow $C2M_HEAD_QUAD (unset = 1).  Per CALLING THREAD (thread_local); measurement and tests.
- */
-int c2m_conv3x3_set_head_stores(int mode);
-
-/*
  * Diagnostics of the pre-filter: after c2m_feature_match_index_f32 took that path the workspace holds int32 [B][Hqp*Wqp]
  * candidate counts at *cnt_offset (-1 = every ref patch was re-scored), int32 [B][Hqp*Wqp][*slots] candidates at
  * *cand_offset (>= 0x40000000: "re-score the whole candidate set of lane (entry & 31)") and int32 flags at *flags_offset
@@ -129,18 +106,31 @@ int c2m_feature_match_filter_tables(int B, int Hq, int Wq, int Hr, int Wr, size_
  *   max_val[b][qy][qx] = that maximum (divided by the query patch norm + 1e-5 when norm_input)
  * with Hqp = (Hq - patch)/in_stride + 1 etc.  max_idx is int64 (torch.max indices), max_val fp32, both [B][Hqp][Wqp].
  * patch == 3, both strides == 1 and C in {64,128,256} run the MFMA sliding-window kernel; everything else runs
- * the generic kernel (same arithmetic, bit-identical results, much slower).  `force_generic` != 0 forces the latter.
+ * the generic kernel (same arithmetic, bit-identical results, much slower).
+ * `flags`: 0 or an OR of the C2M_CORR_* bits below; any other bit gives C2M_ERR_INVALID_ARG.
+ *   C2M_CORR_FORCE_GENERIC  run the generic kernel whatever the shape.
+ *   C2M_CORR_EXACT_SWEEP    the MFMA path has two implementations with identical results (indices AND values):
+ *     exact sweep   every (query, ref patch) score on the fp32 matrix pipe (corr_argmax.hip);
+ *     pre-filter    the same sweep on the f16 matrix pipe (two pieces per operand, three products: 3/16 of the matrix time)
+ *                   keeps, per query, every candidate whose filter score lies within a RIGOROUS error band of the best one
+ *                   (8.4e-5 |query patch| + 1e-6); the listed candidates are then re-scored with the oracle's exact fp32
+ *                   chain and the first maximum taken (corr_filter.hip).  Needs is_norm, |x| < 3.99 everywhere and ref patch
+ *                   norms >= 0.5 (channel-normalised features satisfy all three); anything else falls back to the exact
+ *                   sweep on the device, without a host round trip.
+ *     The pre-filter is the default; this bit skips it and runs the exact sweep only, for this call (measurement and tests).
  */
+#define C2M_CORR_FORCE_GENERIC 1
+#define C2M_CORR_EXACT_SWEEP 2
 int c2m_feature_match_index_f32(c2m_stream_t stream, const float* feat_in, const float* feat_ref, int B, int C,
                                 int Hq, int Wq, int Hr, int Wr, int patch, int in_stride, int ref_stride,
-                                int is_norm, int norm_input, int force_generic, int64_t* max_idx, float* max_val,
+                                int is_norm, int norm_input, int flags, int64_t* max_idx, float* max_val,
                                 void* workspace, size_t workspace_bytes);
 /* The same with the per-pixel sums of squares of one or both maps handed in (ss_in_pre [B][Hq*Wq], ss_ref_pre [B][Hr*Wr]: what
  * c2m_feature_normalize_ss_f32 wrote next to the normalised maps; NULL = computed here).  They must be the canonical chain over
  * THESE maps' values (fmaf, c ascending) -- the patch norms, and with them the index map's bit-exactness, depend on it. */
 int c2m_feature_match_index_pre_f32(c2m_stream_t stream, const float* feat_in, const float* feat_ref, int B, int C,
                                     int Hq, int Wq, int Hr, int Wr, int patch, int in_stride, int ref_stride,
-                                    int is_norm, int norm_input, int force_generic, int64_t* max_idx, float* max_val,
+                                    int is_norm, int norm_input, int flags, int64_t* max_idx, float* max_val,
                                     void* workspace, size_t workspace_bytes, const float* ss_in_pre, const float* ss_ref_pre);
 
 /*
@@ -336,9 +326,11 @@ typedef struct c2m_conv3x3_desc {
 #define C2M_IO_OUT_BF16 2
 #define C2M_IO_RES1_BF16 4
 #define C2M_IO_RES2_BF16 8
-#define C2M_IO_DWORD_STORES 16   /* split algorithms, C2M_OUT_NHWC_PIXEL_SHUFFLE2 / C2M_OUT_NCHW only (alone): take the epilogue's
-                                    one-dword-per-lane stores instead of the 16-byte lane-swapped / quad-transposed ones -- the
-                                    same bits through the other instruction sequence; per call (tests, measurement) */
+#define C2M_IO_DWORD_STORES 16   /* split algorithms, C2M_OUT_NHWC_PIXEL_SHUFFLE2 / C2M_OUT_NCHW / C2M_OUT_DCN_HEAD only (alone): take
+                                    the epilogue's one-dword-per-lane stores instead of the 16-byte lane-swapped / quad-transposed
+                                    ones (DCN head, maps with W % 4 == 0: also one 8-byte flow load per (4 channels, pixel) instead
+                                    of the per-row flow window held in registers) -- the same bits through the other instruction
+                                    sequence; per call (tests, measurement) */
 
 size_t c2m_conv3x3_relayout_bytes(int Cin, int Cout);   /* 0 if the geometry is unsupported (Cin % 32 != 0) */
 int c2m_conv3x3_relayout_f32(c2m_stream_t stream, const float* weight /* [Cout][Cin][3][3] */, int Cin, int Cout, float* wr);

@@ -19,13 +19,13 @@ def test_header_declares_the_expected_entry_points():
         assert must in names
 
 
-def test_library_exports_every_declared_symbol_at_abi_4():
+def test_library_exports_every_declared_symbol_at_abi_5():
     import c2m_amd
     assert os.path.exists(c2m_amd.LIB_PATH), "run __graft_entry__.build() first"
     lib = ctypes.CDLL(c2m_amd.LIB_PATH)
     missing = [n for n in _declared() if not hasattr(lib, n)]
     assert not missing, missing
-    assert lib.c2m_abi_version() == 4
+    assert lib.c2m_abi_version() == 5
     lib.c2m_status_string.restype = ctypes.c_char_p
     assert lib.c2m_status_string(0) == b"ok" and b"workspace" in lib.c2m_status_string(3)
 

@@ -581,9 +581,11 @@ def test_conv3x3_bf16_tensors_views_and_rejections(ops, dev):
 
 @pytest.mark.parametrize("algo", SPLIT_ALGOS)
 def test_dcn_head_on_the_split_kernel(ops, dev, algo):
-    """DCN offset/mask head epilogue of the split kernel (192 + 24 channels): same check as the fp32-MFMA kernels'."""
+    """DCN offset/mask head epilogue of the split kernel (192 + 24 channels): same check as the fp32-MFMA kernels', and the
+    per-call dword store path (dword_stores=True) gives the default call's bits at every shape."""
     import c2m_oracle as oracle
     import synth
+    from c2m_amd._lib import C2MError
     B, C, dg = 2, 64, 8
     # W % 4 != 0: dword planar stores; W % 4 == 0: the quad-transposed 16-byte stores with the per-row flow window (every
     # scale; ragged tiles in x and y; windows that cross 32-pixel tile boundaries)
@@ -606,6 +608,12 @@ def test_dcn_head_on_the_split_kernel(ops, dev, algo):
         assert float((off.double() - (want_off + pre_t)).abs().max()) < tol
         assert float((msk.double() - torch.sigmoid(m)).abs().max()) < 1e-6
         assert abs(float(abs_sum.sum()) - want_abs) < 1e-4 * want_abs
+        abs_dw = torch.zeros(256, dtype=torch.float64, device=dev)
+        off_dw, msk_dw = ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, abs_dw, algo=algo, dword_stores=True)
+        assert torch.equal(off_dw, off) and torch.equal(msk_dw, msk), (h, w, s)
+        assert abs(float(abs_dw.sum()) - want_abs) < 1e-4 * want_abs
+    with pytest.raises(C2MError):   # the store paths belong to the split kernels
+        ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, None, algo="direct", dword_stores=True)
 
 
 @pytest.mark.parametrize("algo", ["split16", "split"])
@@ -621,23 +629,19 @@ def test_dcn_head_store_paths_are_bit_identical_at_full_size(ops, dev, algo):
     hp = h - 2
     idx = (synth.uniform((B, hp, hp), 383, 0.0, 1.0).astype(np.float64) * (hp * hp)).astype(np.int64) % (hp * hp)
     flow = ops.index_to_flow(torch.from_numpy(idx).to(dev))
-    with ops.head_store_mode(0):
-        a0 = torch.zeros(256, dtype=torch.float64, device=dev)
-        off0, msk0 = ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, a0, algo=algo)
+    a0 = torch.zeros(256, dtype=torch.float64, device=dev)
+    off0, msk0 = ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, a0, algo=algo, dword_stores=True)
     for rep in range(3):
-        with ops.head_store_mode(1):
-            a1 = torch.zeros(256, dtype=torch.float64, device=dev)
-            off1, msk1 = ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, a1, algo=algo)
+        a1 = torch.zeros(256, dtype=torch.float64, device=dev)
+        off1, msk1 = ops.conv3x3_dcn_head(feat, wt, bs, dg, flow, s, a1, algo=algo)
         assert torch.equal(off0, off1) and torch.equal(msk0, msk1), rep
         assert abs(float(a0.sum()) - float(a1.sum())) <= 1e-9 * float(a0.sum())
         del off1, msk1
     # the medium stage (scale 2, 128 -> 216): two sources
     f2a, f2b = _cl(_rand((B, 64, 320, 320), dev, 384)), _cl(_rand((B, 64, 320, 320), dev, 385))
     w2, b2 = _rand((3 * dg * 9, 128, 3, 3), dev, 386, 0.02), _rand((3 * dg * 9,), dev, 387, 0.1)
-    with ops.head_store_mode(0):
-        r0 = ops.conv3x3_dcn_head([f2a, f2b], w2, b2, dg, flow, 2, None, algo=algo)
-    with ops.head_store_mode(1):
-        r1 = ops.conv3x3_dcn_head([f2a, f2b], w2, b2, dg, flow, 2, None, algo=algo)
+    r0 = ops.conv3x3_dcn_head([f2a, f2b], w2, b2, dg, flow, 2, None, algo=algo, dword_stores=True)
+    r1 = ops.conv3x3_dcn_head([f2a, f2b], w2, b2, dg, flow, 2, None, algo=algo)
     assert torch.equal(r0[0], r1[0]) and torch.equal(r0[1], r1[1])
 
 

@@ -350,9 +350,10 @@ def test_all_duplicate_middle_band_keeps_later_tiles_live(env, dev):
 
 
 def test_filter_mode_reaches_launches_from_worker_threads(env, dev):
-    """the library's A/B switch is thread_local; `with ops.corr_filter_mode(0)` opened on the main thread must still
-    govern a launch made from a worker thread (nn.DataParallel replicas launch from such threads) -- the op wrapper re-applies
-    the recorded mode on the launching thread.  Observed through the kernel names the profiler records."""
+    """`with ops.corr_filter_mode(0)` opened on the main thread must still govern a launch made from a worker thread
+    (nn.DataParallel replicas launch from such threads).  It does because the mode is a per-call argument of the library: the
+    op wrapper reads the block's default on the launching thread and passes it in that launch's flags word; no per-thread
+    library state exists.  Observed through the kernel names the profiler records."""
     import threading
     import c2m_amd
     ops, oracle, synth = env
@@ -376,6 +377,35 @@ def test_filter_mode_reaches_launches_from_worker_threads(env, dev):
         c2m_amd.profile_enable(False)
     assert "corr_argmax_mfma" in seen["exact"] and "corr_filter" not in seen["exact"], seen
     assert "corr_filter" in seen["filter"], seen
+
+
+def test_exact_sweep_argument_selects_the_path_per_call(env, dev):
+    """`exact_sweep=True` runs the exact fp32 sweep alone, the default call the pre-filter, and an explicit `exact_sweep=False`
+    wins over an enclosing `corr_filter_mode(0)`; all three give the same indices and values.  Kernel names from the profiler."""
+    import c2m_amd
+    ops, oracle, synth = env
+    fi = _t(oracle.feature_normalize(synth.gaussish((256, 20, 20), 71))[None], dev)
+    fr = _t(oracle.feature_normalize(synth.gaussish((256, 24, 24), 72))[None], dev)
+    seen, res = {}, {}
+
+    def launch(tag, **kw):
+        c2m_amd.profile_enable(True)
+        c2m_amd.profile_collect()
+        try:
+            res[tag] = ops.feature_match_index_batched(fi, fr, 3, 1, 1, True, True, **kw)
+            torch.cuda.synchronize()
+            seen[tag] = {n for n, _ in c2m_amd.profile_collect()}
+        finally:
+            c2m_amd.profile_enable(False)
+
+    launch("exact", exact_sweep=True)
+    launch("default")
+    with ops.corr_filter_mode(0):
+        launch("explicit", exact_sweep=False)
+    assert "corr_argmax_mfma" in seen["exact"] and "corr_filter" not in seen["exact"], seen
+    assert "corr_filter" in seen["default"] and "corr_filter" in seen["explicit"], seen
+    for tag in ("default", "explicit"):
+        assert torch.equal(res[tag][0], res["exact"][0]) and torch.equal(res[tag][1], res["exact"][1]), tag
 
 
 def test_sums_of_squares_from_the_normalisation_kernel_change_nothing(env, dev):
