@@ -103,6 +103,12 @@ def _declare(L):
     L.c2m_conv3x3_wgrad_workspace_bytes.argtypes = [_i] * 5
     L.c2m_conv3x3_wgrad_f32.argtypes = [_vp, ctypes.POINTER(ConvSrc), _i, _vp, _i, _i, ctypes.c_longlong] + [_i] * 5 + [_vp, _vp, _sz]
     L.c2m_conv3x3_nhwc_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Desc)]
+    L.c2m_conv3x3_nhwc_roi_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Desc), _i, _i]
+    L.c2m_conv3x3_rgb64_roi_f32.argtypes = L.c2m_conv3x3_rgb64_f32.argtypes + [_i, _i]
+    L.c2m_conv3x3_roi_tile.argtypes = [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)]
+    L.c2m_ref_live_extent_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp]
+    _ll = ctypes.c_longlong
+    L.c2m_band_fill_f32.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _vp, _i, _i, _i, _i, _ll] + [_i] * 5
     L.c2m_index_to_flow_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp]
     L.c2m_contras_loss_workspace_bytes.restype = _sz
     L.c2m_contras_loss_workspace_bytes.argtypes = [_i] * 6

@@ -659,7 +659,18 @@ class conv_flavour:
 
 def f16_range_guard(owner, fn, device):
     """Run `fn()` (a fused forward made of conv3x3 calls) so that it never returns f16 x 2 overflow garbage: see above.
-    `owner` (an nn.Module or any object) remembers the pinned flavour in `owner._c2m_conv_bf16x3`."""
+    `owner` (an nn.Module or any object) remembers the pinned flavour in `owner._c2m_conv_bf16x3`.
+    The outermost guard is also the scope in which the Ref's live extent is shared (ref_live_extent_shared)."""
+    if getattr(_tls, "live_cache", None) is not None:
+        return _f16_range_guard(owner, fn, device)
+    _tls.live_cache = {}
+    try:
+        return _f16_range_guard(owner, fn, device)
+    finally:
+        _tls.live_cache = None
+
+
+def _f16_range_guard(owner, fn, device):
     if getattr(_tls, "guarded", False):      # an enclosing guard (a parent module's forward) checks the flag for all of us
         return fn()
     # (under bf16 autocast the convolutions run the bf16 flavour and never touch the flag; the DCNv2 forwards -- fp32 under
@@ -758,17 +769,31 @@ def _desc_out(d, out, bf16_ok=False):
     return o
 
 
-def _launch_conv(d, dev, kind, family_prefix=""):
-    """c2m_conv3x3_nhwc_f32 on the current stream of `dev` (+ the opt-in flop accounting of the launch)."""
+def _roi_pixels(roi_tiles, H, W, rgb64=False):
+    """(rows, columns) of the pixels a launch computes: the whole map, or the top-left `roi_tiles` = (tile rows, tile columns)."""
+    if roi_tiles is None:
+        return H, W
+    th, tw = conv_roi_tile(rgb64)
+    return min(roi_tiles[0] * th, H), min(roi_tiles[1] * tw, W)
+
+
+def _launch_conv(d, dev, kind, family_prefix="", roi_tiles=None):
+    """c2m_conv3x3_nhwc_f32 (roi_tiles: c2m_conv3x3_nhwc_roi_f32, the top-left (tile rows, tile columns) only) on the current
+    stream of `dev` (+ the opt-in flop accounting of the launch: the pixels of the tiles actually launched)."""
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
+        if roi_tiles is None:
+            _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
+        else:
+            _lib.check(_lib.lib().c2m_conv3x3_nhwc_roi_f32(_stream(), d, int(roi_tiles[0]), int(roi_tiles[1])),
+                       "c2m_conv3x3_nhwc_roi_f32")
     if _ConvFlops.enabled:
-        f = 2.0 * d.Cout * 9 * d.Cin * d.H * d.W * d.B
+        rh, rw = _roi_pixels(roi_tiles, d.H, d.W)
+        f = 2.0 * d.Cout * 9 * d.Cin * rh * rw * d.B
         _ConvFlops.add(family_prefix + _KINDS[kind].family, f, f * _KINDS[kind].exec_factor)
 
 
 def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=None, out_mode="nhwc", out=None, algo=None,
-            out2_grouped8=None, fast=False, out_dtype=None, dword_stores=False):
+            out2_grouped8=None, fast=False, out_dtype=None, dword_stores=False, roi_tiles=None):
     """out = act(conv3x3(cat(srcs, dim=1)) + bias) + res1 + res2 on channels-last tensors, one kernel.
 
     bf16 tensors ("bf16" kernel and "nhwc" mode only -- what a bf16-autocast forward keeps its activations in between fused
@@ -790,6 +815,8 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
     dword_stores: split kernels, "pixel_shuffle" / "nchw" modes: this call's epilogue stores one dword per lane instead of
     the 16-byte lane-swapped / quad-transposed pieces (c2m_hip.h C2M_IO_DWORD_STORES: same bits, the other instruction
     sequence -- tests and measurement; per call, nothing process-wide).
+    roi_tiles: (tile rows, tile columns) -- split kernels only: launch the top-left tiles of the grid (conv_roi_tile() pixels
+    each) and leave the rest of the output untouched (the Ref-side towers fill it from a template: _RefBand).
     $C2M_CONV_SPLIT=1 restricts it to calls with fast=True (the decoder; the extractor towers that feed the index search
     then stay on the fp32-MFMA kernels), $C2M_CONV_SPLIT=0 restores the round-2 choice everywhere: Winograd F(4,3) with
     fast=True / F(2,3) where the shapes allow, else direct."""
@@ -867,7 +894,9 @@ def conv3x3(srcs, weight, bias=None, act=ACT_NONE, slope=0.1, res1=None, res2=No
         d.out = out.data_ptr()
     else:
         raise _lib.C2MError(f"unknown out_mode {out_mode}")
-    _launch_conv(d, dev, kind)
+    if roi_tiles is not None and kind not in _SPLIT_KINDS:
+        raise _lib.C2MError("conv3x3: roi_tiles needs one of the split kernels")
+    _launch_conv(d, dev, kind, roi_tiles=roi_tiles)
     return out
 
 
@@ -985,10 +1014,12 @@ def _grouped8_args(g2, B, Cout, H, W, dev):
     return g2.data_ptr() + ((W + 3) + 1) * 8 * 4, (W + 3) * 8, (H + 3) * (W + 3) * 8, (Cout // 8) * (H + 3) * (W + 3) * 8
 
 
-def conv3x3_rgb64(image, weight, bias=None, act=ACT_NONE, slope=0.1, mean=None, std=None, out=None, out2_grouped8=None):
+def conv3x3_rgb64(image, weight, bias=None, act=ACT_NONE, slope=0.1, mean=None, std=None, out=None, out2_grouped8=None,
+                  roi_tiles=None):
     """First layer of an image tower (3 -> 64 channels; vgg conv1_1, conv_first) as its own im2col kernel:
     out = act(conv3x3((image - mean) / std) + bias), channels_last [B,64,H,W].  image: [B,3,H,W] (any layout; read as
-    contiguous NCHW); mean / std: [1,3,1,1] buffers of the extractor or None.  out / out2_grouped8 as in conv3x3."""
+    contiguous NCHW); mean / std: [1,3,1,1] buffers of the extractor or None.  out / out2_grouped8 / roi_tiles as in conv3x3
+    (the tile of this kernel: conv_roi_tile(rgb64=True))."""
     if image.dim() != 4 or image.shape[1] != 3 or not image.is_cuda:
         raise _lib.C2MError("conv3x3_rgb64: image must be a GPU tensor [B,3,H,W]")
     if tuple(weight.shape) != (64, 3, 3, 3):
@@ -1012,14 +1043,18 @@ def conv3x3_rgb64(image, weight, bias=None, act=ACT_NONE, slope=0.1, mean=None, 
     if tuple(out.shape) != (B, 64, H, W):
         raise _lib.C2MError("conv3x3_rgb64: out must be [B,64,H,W]")
     o2, o2_row, o2_plane, o2_img = _grouped8_args(out2_grouped8, B, 64, H, W, dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().c2m_conv3x3_rgb64_f32(
-            _stream(), x.data_ptr(), B, H, W, w.data_ptr(), bias.data_ptr() if bias is not None else None,
+    args = (x.data_ptr(), B, H, W, w.data_ptr(), bias.data_ptr() if bias is not None else None,
             mean.data_ptr() if mean is not None else None, std.data_ptr() if std is not None else None, int(act),
-            float(slope), out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch, o2, o2_row, o2_plane, o2_img),
-            "c2m_conv3x3_rgb64_f32")
+            float(slope), out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch, o2, o2_row, o2_plane, o2_img)
+    with torch.cuda.device(dev):
+        if roi_tiles is None:
+            _lib.check(_lib.lib().c2m_conv3x3_rgb64_f32(_stream(), *args), "c2m_conv3x3_rgb64_f32")
+        else:
+            _lib.check(_lib.lib().c2m_conv3x3_rgb64_roi_f32(_stream(), *args, int(roi_tiles[0]), int(roi_tiles[1])),
+                       "c2m_conv3x3_rgb64_roi_f32")
     if _ConvFlops.enabled:
-        _ConvFlops.add("rgb_first_layer", 2.0 * 64 * 27 * H * W * B, 2.0 * 64 * 28 * H * W * B)
+        rh, rw = _roi_pixels(roi_tiles, H, W, rgb64=True)
+        _ConvFlops.add("rgb_first_layer", 2.0 * 64 * 27 * rh * rw * B, 2.0 * 64 * 28 * rh * rw * B)
     return out
 
 
@@ -1224,6 +1259,207 @@ def dcn_v2_forward_nhwc(inp_bordered, weight, bias, offset, mask, deformable_gro
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# The padding band of a zero-padded Ref (csrc/ref_band.hip): behind the live region plus a layer's receptive radius a
+# Ref-side feature map depends on the distances to the canvas edges only.  The Ref towers launch their convolutions on the
+# top-left tiles, run the same layers on a small all-zero canvas (the template) and copy the band from it: the same bits.
+# ---------------------------------------------------------------------------------------------------------------------
+_ref_band_on = True   # what the fused Ref-side forwards do by default; ref_band_mode saves, sets and restores it
+
+
+class ref_band_mode:
+    """`with ops.ref_band_mode(0): ...` -- the Ref-side towers launch every tile (the path before the band fill); (1): live
+    tiles + band fill (default).  Results are identical; for every thread's forwards through this module while the block is
+    open (measurement / tests).  Per call: vgg_stack_forward(live=...)."""
+
+    def __init__(self, mode):
+        self.mode = int(mode)
+        if self.mode not in (0, 1):
+            raise _lib.C2MError("ref_band_mode: 0 or 1")
+
+    def __enter__(self):
+        global _ref_band_on
+        self.prev, _ref_band_on = _ref_band_on, self.mode == 1
+        return self
+
+    def __exit__(self, *exc):
+        global _ref_band_on
+        _ref_band_on = self.prev
+        return False
+
+
+def conv_roi_tile(rgb64=False):
+    """(rows, columns) of the pixel tile of a workgroup: of conv3x3_rgb64's kernel, or of the split kernels (what `roi_tiles`
+    counts; c2m_conv3x3_roi_tile: host-side, no GPU needed)."""
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().c2m_conv3x3_roi_tile(int(bool(rgb64)), ctypes.byref(th), ctypes.byref(tw)), "c2m_conv3x3_roi_tile")
+    return th.value, tw.value
+
+
+def band_src_index(v, n, t, margin):
+    """The fill's edge-distance clamp (csrc/ref_band.hip band_src) for coordinate v of an extent n and a template extent t."""
+    return v if v < margin else (t - (n - v) if n - v <= margin else margin)
+
+
+def stack_geometry(layers):
+    """['conv' | 'pool', ...] of an ordered {name: layer} stack (ReLUs dropped): what ref_band_plan walks."""
+    return ["conv" if isinstance(m, torch.nn.Conv2d) else "pool" for m in layers.values()
+            if isinstance(m, (torch.nn.Conv2d, torch.nn.MaxPool2d))]
+
+
+def ref_band_plan(geometry, H, W, live_h, live_w, first_rgb64=True, tiles=None):
+    """Host arithmetic of the band path for a stack of 3x3 / pad 1 convolutions and 2x2 / stride 2 pools on an H x W canvas whose
+    non-zero pixels lie inside [0, live_h) x [0, live_w).  geometry: ['conv' | 'pool', ...] in order.  tiles: ((th, tw) of the
+    first-layer kernel, (th, tw) of the split kernels), default: the library's.  Per convolution, at its own resolution (scale
+    s = 2^pools before it): R = its cumulative receptive radius in full-resolution pixels (each convolution adds s), the extent
+    that can differ from the band ceil((live + R) / s), and that extent in whole tiles.  -> None where the path declines (no
+    layer would skip a tile, or a map is too small to have an interior), else
+    {'convs': [{'scale', 'radius', 'extent': (h, w), 'tile': (th, tw), 'tiles': (rows, columns), 'roi': (rows, columns)}, ...],
+     'template': (Ht, Wt)}: the template canvas has >= 2 R + 2 coarsest-scale tiles on every side."""
+    if tiles is None:
+        tiles = (conv_roi_tile(True), conv_roi_tile(False))
+    n_pool = sum(1 for g in geometry if g == "pool")
+    if live_h is None or live_w is None or H % (1 << n_pool) != 0 or W % (1 << n_pool) != 0 or (live_h >= H and live_w >= W):
+        return None
+    convs, s, R, any_saved = [], 1, 0, False
+    for k, g in enumerate(geometry):
+        if g == "pool":
+            s *= 2
+            continue
+        R += s
+        th, tw = tiles[0] if (k == 0 and first_rgb64) else tiles[1]
+        Hc, Wc = H // s, W // s
+        full = (-(-Hc // th), -(-Wc // tw))
+        ext = (-(-(live_h + R) // s), -(-(live_w + R) // s))
+        roi = (max(1, min(full[0], -(-ext[0] // th))), max(1, min(full[1], -(-ext[1] // tw))))
+        any_saved |= roi != full
+        convs.append({"scale": s, "radius": R, "extent": ext, "tile": (th, tw), "tiles": full, "roi": roi})
+    if not convs or not any_saved:
+        return None
+    align = 4 * s
+    th, tw = tiles[1]
+    Ht = -(-(2 * R + 2 * s * th) // align) * align
+    Wt = -(-(2 * R + 2 * s * tw) // align) * align
+    for c in convs:   # every map (and its pooled successor: scale 2 s) keeps three disjoint zones of the clamp
+        for sc in (c["scale"], 2 * c["scale"]):
+            m = band_margin(c["radius"], sc)
+            if min(H // sc, W // sc, Ht // sc, Wt // sc) < 2 * m + 1:
+                return None
+    return {"convs": convs, "template": (Ht, Wt)}
+
+
+def band_margin(radius, scale):
+    """Pixels (at `scale`) from a canvas edge within which a map of receptive radius `radius` (full-resolution pixels) may see
+    that edge: ceil(radius / scale), plus one to spare."""
+    return -(-radius // scale) + 1
+
+
+def ref_live_extent(img):
+    """img [B,3,H,W] float32 on the GPU -> (live_h, live_w) host ints: the bounding box, anchored at (0, 0), of the pixels that
+    are not exactly 0.0 in all three channels, over the batch.  One kernel launch and one 8-byte read-back."""
+    if not img.is_cuda or img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32 or not img.is_contiguous():
+        raise _lib.C2MError("ref_live_extent: a contiguous float32 GPU tensor [B,3,H,W]")
+    B, _, H, W = img.shape
+    ext = torch.zeros(2, dtype=torch.int32, device=img.device)
+    with torch.cuda.device(img.device):
+        _lib.check(_lib.lib().c2m_ref_live_extent_f32(_stream(), img.data_ptr(), B, H, W, ext.data_ptr()), "c2m_ref_live_extent_f32")
+    lh, lw = ext.tolist()
+    return int(lh), int(lw)
+
+
+def ref_live_extent_shared(img):
+    """ref_live_extent(img) for the fused Ref-side forwards, or None where the band path does not apply (switched off, not a
+    contiguous float32 GPU image, a stream capture: no read-back).  Inside an f16_range_guard -- one inference step of
+    RefRestorationModel.test() / bench.py -- the extent of an image is read once and shared by the modules of that step; it
+    is never kept across guards."""
+    if (not _ref_band_on or not isinstance(img, torch.Tensor) or not img.is_cuda or img.dim() != 4 or img.shape[1] != 3 or
+            img.dtype != torch.float32 or not img.is_contiguous() or img.numel() >= 2 ** 31 or
+            torch.cuda.is_current_stream_capturing()):
+        return None
+    cache = getattr(_tls, "live_cache", None)
+    key = (img.data_ptr(), tuple(img.shape), img._version, img.device)
+    if cache is not None and key in cache:
+        return cache[key]
+    live = ref_live_extent(img)
+    if cache is not None:
+        cache[key] = live
+    return live
+
+
+def band_fill(dst, tmpl, roi_h, roi_w, margin_y, margin_x, layout="nhwc"):
+    """Write every pixel of `dst` outside [0, roi_h) x [0, roi_w) from the one-sample template through the edge-distance clamp
+    (c2m_band_fill_f32).  layout "nhwc": logical [B,C,H,W] tensors with channel stride 1 (channels-last tensors, interior views
+    of bordered buffers); "grouped8": zero-bordered group-major buffers [B,C/8,H+3,W+3,8]; "nchw": contiguous [B,C,H,W]."""
+    L = _lib.lib()
+    if layout == "grouped8":
+        B, G, Hb, Wb, e = dst.shape
+        _, Gt, Htb, Wtb, et = tmpl.shape
+        if e != 8 or et != 8 or G != Gt or not dst.is_contiguous() or not tmpl.is_contiguous() or tmpl.shape[0] != 1:
+            raise _lib.C2MError("band_fill: grouped8 buffers are contiguous [B, C/8, H+3, W+3, 8]")
+        H, W, Ht, Wt = Hb - 3, Wb - 3, Htb - 3, Wtb - 3
+        args = (dst.data_ptr() + (Wb + 1) * 32, B, G * 8, H, W, 8, 8, Wb * 8, Hb * Wb * 8, G * Hb * Wb * 8,
+                tmpl.data_ptr() + (Wtb + 1) * 32, Ht, Wt, 8, Wtb * 8, Htb * Wtb * 8)
+        planar = 0
+    elif layout == "nhwc":
+        B, C, H, W = dst.shape
+        Ht, Wt = tmpl.shape[2:]
+        d, t = _nhwc_src(dst, "dst"), _nhwc_src(tmpl, "tmpl")
+        if tmpl.shape[0] != 1 or tmpl.shape[1] != C:
+            raise _lib.C2MError("band_fill: the template is [1, C, Ht, Wt]")
+        args = (dst.data_ptr(), B, C, H, W, C, d.pix_pitch, d.row_pitch, 0, d.img_pitch,
+                tmpl.data_ptr(), Ht, Wt, t.pix_pitch, t.row_pitch, 0)
+        planar = 0
+    elif layout == "nchw":
+        B, C, H, W = dst.shape
+        Ht, Wt = tmpl.shape[2:]
+        if not dst.is_contiguous() or not tmpl.is_contiguous() or tuple(tmpl.shape[:2]) != (1, C):
+            raise _lib.C2MError("band_fill: nchw tensors are contiguous, the template [1, C, Ht, Wt]")
+        args = (dst.data_ptr(), B, C, H, W, 1, 0, 0, 0, 0, tmpl.data_ptr(), Ht, Wt, 0, 0, 0)
+        planar = 1
+    else:
+        raise _lib.C2MError(f"band_fill: unknown layout {layout}")
+    if dst.dtype != torch.float32 or tmpl.dtype != torch.float32 or not dst.is_cuda or tmpl.device != dst.device:
+        raise _lib.C2MError("band_fill: float32 GPU tensors on one device")
+    with torch.cuda.device(dst.device):
+        _lib.check(L.c2m_band_fill_f32(_stream(), *args, int(roi_h), int(roi_w), int(margin_y), int(margin_x), planar),
+                   "c2m_band_fill_f32")
+    return dst
+
+
+class _RefBand:
+    """State of one vgg_stack_forward on the band path: the plan, the template's current activation and the position in
+    both.  conv() runs one layer: the template (every tile, B = 1), the image (the plan's tiles) and the fill."""
+
+    def __init__(self, plan, H, W, dev, algo):
+        self.plan, self.H, self.W, self.algo, self.k = plan, H, W, algo, 0
+        self.tcur = torch.zeros((1, 3) + tuple(plan["template"]), dtype=torch.float32, device=dev)
+
+    def conv(self, call, first, src, cout, out_mode, out, out2):
+        c = self.plan["convs"][self.k]
+        self.k += 1
+        # the same kernel kind and arithmetic for the template as for the image, whatever the size-dependent rules would pick
+        extra = {} if first else {"algo": self.algo}
+        t2 = None
+        if out2 is not None:
+            t2 = torch.empty((1, cout // 8, self.tcur.shape[2] + 3, self.tcur.shape[3] + 3, 8), dtype=torch.float32, device=src.device)
+        t_out = call(self.tcur, None, t2, **extra)
+        self.tcur = t_out
+        if c["roi"] == c["tiles"]:
+            return call(src, out, out2, **extra)
+        res = call(src, out, out2, roi_tiles=c["roi"], **extra)
+        pooled = out_mode == "nhwc_pool2"
+        so = c["scale"] * (2 if pooled else 1)
+        Hc, Wc = self.H // c["scale"], self.W // c["scale"]
+        roi_h, roi_w = min(c["roi"][0] * c["tile"][0], Hc), min(c["roi"][1] * c["tile"][1], Wc)
+        if pooled:
+            roi_h, roi_w = roi_h // 2, roi_w // 2
+        m = band_margin(c["radius"], so)
+        band_fill(res, t_out, roi_h, roi_w, m, m, layout="nchw" if out_mode == "nchw" else "nhwc")
+        if out2 is not None:
+            band_fill(out2, t2, roi_h, roi_w, m, m, layout="grouped8")
+        return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # VGG-style feature stacks (conv3x3 + ReLU + 2x2 max-pool) on the channels-last kernels
 # ---------------------------------------------------------------------------------------------------------------------
 def _bordered_empty(B, C, H, W, device, grouped8=False):
@@ -1256,7 +1492,13 @@ def _pool_is_2x2(m):
     return two(m.kernel_size) and two(m.stride) and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1)) and not m.ceil_mode
 
 
-def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, grouped8_taps=(), fast=False):
+def _band_split_ok(layer, fast):
+    """conv3x3's automatic choice for this layer is a split kernel at every map size (what the band path launches by name)."""
+    co, ci = layer.weight.shape[:2]
+    return (_SPLIT == "all" or ((fast or bf16_autocast()) and _SPLIT != "0")) and ci % 16 == 0 and co % 4 == 0
+
+
+def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, grouped8_taps=(), fast=False, live=None):
     """Run an ordered {name: nn.Conv2d(3x3, pad 1) | nn.ReLU | nn.MaxPool2d(2, 2)} stack (torchvision's vgg `features`
     layout, mmsr/models/archs/vgg_arch.py:107-123) on the fused channels-last convolution: every conv + its ReLU is one
     launch.  x: [B,3,H,W] image; (x - mean) / std is applied while the image is widened to the kernel's 32-channel chunk.
@@ -1266,7 +1508,9 @@ def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, 
     tensor under the key of that layer (the correlation kernels read planar features).  grouped8_taps: taps that also get
     the group-major twin (BorderedNHWC.grouped8) a DCNv2 layer with 8-channel deformable groups gathers from.  fast: as in
     conv3x3 (the split-bf16 kernel for every layer but the first): the VGG taps of the Ref do, the extractor towers that feed
-    the index search do not."""
+    the index search do not.  live: (live_h, live_w) of a zero-padded Ref (ref_live_extent) or None -- the convolutions launch
+    only the tiles the live region reaches and the band behind them is filled from a template (_RefBand): the same bits.  The
+    path declines (every tile is launched) where no tile would be skipped or the stack is not one it covers."""
     names = list(layers.keys())
     B, C, H, W = x.shape
     dev = x.device
@@ -1283,12 +1527,27 @@ def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, 
             xin = (xin - mean) / std
         cur[:, :C] = xin
     out, k = {}, 0
+    band = None
+    convs_ = [m for m in layers.values() if isinstance(m, torch.nn.Conv2d)]
+    if (live is not None and rgb64 and x.dtype == torch.float32 and
+            all(isinstance(m, (torch.nn.Conv2d, torch.nn.ReLU)) or (isinstance(m, torch.nn.MaxPool2d) and _pool_is_2x2(m))
+                for m in layers.values()) and
+            all(m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1) and m.groups == 1 for m in convs_) and
+            all(_band_split_ok(m, fast) for m in convs_[1:])):
+        plan = ref_band_plan(stack_geometry(layers), H, W, live[0], live[1])
+        if plan is not None:
+            band = _RefBand(plan, H, W, dev, _KINDS[_split_kind(None)].name)
 
-    def conv(k_, src, layer_, **kw):
-        if k_ == 0 and rgb64:
-            kw.pop("algo", None)
-            return conv3x3_rgb64(src, layer_.weight, layer_.bias, mean=mean, std=std, **kw)
-        return conv3x3(src, layer_.weight, layer_.bias, fast=fast, **kw)
+    def conv(k_, src, layer_, act=ACT_NONE, out_mode="nhwc", out=None, out2_grouped8=None):
+        first = k_ == 0 and rgb64
+
+        def call(src_, out_, out2_, **kw):
+            if first:
+                return conv3x3_rgb64(src_, layer_.weight, layer_.bias, act=act, mean=mean, std=std, out=out_, out2_grouped8=out2_, **kw)
+            return conv3x3(src_, layer_.weight, layer_.bias, act=act, out_mode=out_mode, out=out_, out2_grouped8=out2_, fast=fast, **kw)
+        if band is None:
+            return call(src, out, out2_grouped8)
+        return band.conv(call, first, src, layer_.out_channels, out_mode, out, out2_grouped8)
 
     while k < len(names):
         name, layer = names[k], layers[names[k]]
@@ -1306,7 +1565,7 @@ def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, 
                     Hc % 2 == 0 and Wc % 2 == 0 and
                     (_wino_ok([cur], layer.weight, "nhwc_pool2", Wc) or _split_ok([cur], layer.weight, fast)))
             if last and last_nchw:
-                cur = conv3x3(cur, layer.weight, layer.bias, act=ACT_RELU if relu else ACT_NONE, out_mode="nchw", fast=fast)
+                cur = conv(-1, cur, layer, act=ACT_RELU if relu else ACT_NONE, out_mode="nchw")
                 out[names[k + 1] if relu else name] = cur
             elif tap_name is not None:
                 bo = _bordered_empty(Bc, layer.out_channels, Hc, Wc, dev, grouped8=tap_name in grouped8_taps)
@@ -1316,16 +1575,20 @@ def vgg_stack_forward(layers, x, taps=(), mean=None, std=None, last_nchw=False, 
                 out[tap_name] = view
                 cur = view
             elif pool:   # conv -> ReLU -> MaxPool2d(2, 2) in one launch: only the pooled map is written
-                cur = conv3x3(cur, layer.weight, layer.bias, act=ACT_RELU, out_mode="nhwc_pool2", fast=fast)
+                cur = conv(k, cur, layer, act=ACT_RELU, out_mode="nhwc_pool2")
                 k += 1   # (the pool layer)
             else:
                 cur = conv(k, cur, layer, act=ACT_RELU if relu else ACT_NONE)
             k += 2 if relu else 1
         elif isinstance(layer, torch.nn.MaxPool2d):
             cur = torch.nn.functional.max_pool2d(cur, layer.kernel_size, layer.stride, layer.padding)
+            if band is not None:
+                band.tcur = torch.nn.functional.max_pool2d(band.tcur, layer.kernel_size, layer.stride, layer.padding)
             k += 1
         elif isinstance(layer, torch.nn.ReLU):
             cur = torch.relu(cur)
+            if band is not None:
+                band.tcur = torch.relu(band.tcur)
             k += 1
         else:
             raise _lib.C2MError(f"vgg_stack_forward: unsupported layer {name}: {type(layer).__name__}")

@@ -1435,7 +1435,7 @@ namespace c2m {
 namespace conv {   // conv3x3_split.hip
 size_t split_relayout_bytes(int Cin, int Cout, int np);
 int split_relayout(hipStream_t st, const float* weight, int Cin, int Cout, int np, void* wr, int dgrad);
-int launch_split(hipStream_t st, Params p, int np);
+int launch_split(hipStream_t st, Params p, int np, int roi_tiles_y = 0, int roi_tiles_x = 0);
 int split_relayout_multi(hipStream_t st, const long long* jobs, int njobs, long long nblocks, int any_f16);
 }  // namespace conv
 }  // namespace c2m
@@ -1509,10 +1509,12 @@ extern "C" int c2m_conv3x3_relayout_wino_f32(c2m_stream_t stream, const float* w
   return check_launch();
 }
 
-extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                                     const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
-                                     int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
-                                     int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch) {
+// roi_tiles_y / roi_tiles_x > 0: only the top-left tiles of the grid (c2m_conv3x3_rgb64_roi_f32)
+static int conv3x3_rgb64_launch(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
+                                const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
+                                int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
+                                int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch, int roi_tiles_y,
+                                int roi_tiles_x) {
   if (!image || !weight || !out || B <= 0 || H <= 0 || W <= 0 || (mean == nullptr) != (std_ == nullptr)) return C2M_ERR_INVALID_ARG;
   if (act < 0 || act > 2 || (act == C2M_ACT_LEAKY_RELU && !(slope >= 0.0f && slope <= 1.0f))) return C2M_ERR_UNSUPPORTED;
   if (out_pix_pitch % 4 != 0 || out_row_pitch % 4 != 0 || out_img_pitch % 4 != 0 || ((uintptr_t)out & 15)) return C2M_ERR_UNSUPPORTED;
@@ -1522,6 +1524,10 @@ extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, in
   p.in = image; p.w = weight; p.bias = bias; p.mean = mean; p.std_ = std_;
   p.B = B; p.H = H; p.W = W;
   p.tiles_x = ceil_div(W, conv::c3::CTW); p.tiles_y = ceil_div(H, conv::c3::CTH);
+  if (roi_tiles_y > 0 && roi_tiles_x > 0) {
+    if (roi_tiles_y > p.tiles_y || roi_tiles_x > p.tiles_x) return C2M_ERR_INVALID_ARG;
+    p.tiles_y = roi_tiles_y; p.tiles_x = roi_tiles_x;
+  }
   p.act = act; p.slope = slope; p.out = out; p.out_pix_pitch = out_pix_pitch; p.out_row_pitch = out_row_pitch;
   p.out_img_pitch = out_img_pitch; p.out2 = out2; p.out2_row_pitch = out2_row_pitch; p.out2_plane_pitch = out2_plane_pitch;
   p.out2_img_pitch = out2_img_pitch;
@@ -1544,6 +1550,31 @@ extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, in
   return check_launch();
 }
 
+extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
+                                     const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
+                                     int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
+                                     int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch) {
+  return conv3x3_rgb64_launch(stream, image, B, H, W, weight, bias, mean, std_, act, slope, out, out_pix_pitch, out_row_pitch,
+                              out_img_pitch, out2, out2_row_pitch, out2_plane_pitch, out2_img_pitch, 0, 0);
+}
+
+extern "C" int c2m_conv3x3_rgb64_roi_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
+                                         const float* bias, const float* mean, const float* std_, int act, float slope,
+                                         float* out, int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
+                                         int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch,
+                                         int roi_tiles_y, int roi_tiles_x) {
+  if (roi_tiles_y <= 0 || roi_tiles_x <= 0) return C2M_ERR_INVALID_ARG;
+  return conv3x3_rgb64_launch(stream, image, B, H, W, weight, bias, mean, std_, act, slope, out, out_pix_pitch, out_row_pitch,
+                              out_img_pitch, out2, out2_row_pitch, out2_plane_pitch, out2_img_pitch, roi_tiles_y, roi_tiles_x);
+}
+
+extern "C" int c2m_conv3x3_roi_tile(int rgb64, int* tile_h, int* tile_w) {
+  if (!tile_h || !tile_w) return C2M_ERR_INVALID_ARG;
+  *tile_h = rgb64 ? conv::c3::CTH : conv::kSplitTileH;
+  *tile_w = rgb64 ? conv::c3::CTW : conv::kSplitTileW;
+  return C2M_OK;
+}
+
 extern "C" int c2m_index_to_flow_f32(c2m_stream_t stream, const int64_t* max_idx, int B, int hq, int wq, float* flow) {
   if (!max_idx || !flow || B <= 0 || hq <= 0 || wq <= 0) return C2M_ERR_INVALID_ARG;
   const int n = B * hq * wq;
@@ -1552,7 +1583,8 @@ extern "C" int c2m_index_to_flow_f32(c2m_stream_t stream, const int64_t* max_idx
   return check_launch();
 }
 
-extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d) {
+// roi_tiles_y / roi_tiles_x > 0: only the top-left tiles of the grid, split kernels only (c2m_conv3x3_nhwc_roi_f32)
+static int conv3x3_nhwc_launch(c2m_stream_t stream, const c2m_conv3x3_desc* d, int roi_tiles_y, int roi_tiles_x) {
   if (!d || !d->wr || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->nsrc < 1 ||
       d->nsrc > 2 || !d->src[0].ptr || (d->nsrc == 2 && !d->src[1].ptr))
     return C2M_ERR_INVALID_ARG;
@@ -1560,6 +1592,7 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   const bool wino = d->algo == C2M_CONV_WINOGRAD_F23X || wino4;   // both: 16-channel chunks, 64-cout blocks
   const bool splitk = d->algo == C2M_CONV_SPLIT_BF16X3 || d->algo == C2M_CONV_BF16 || d->algo == C2M_CONV_SPLIT_F16X2;   // 16-channel chunks, any shape
   if (d->algo != 0 && !wino && !splitk) return C2M_ERR_INVALID_ARG;
+  if (roi_tiles_y > 0 && !splitk) return C2M_ERR_UNSUPPORTED;
   if (splitk && (d->out2 || (d->out_mode == 4 && (d->H % 2 != 0 || d->W % 2 != 0 || d->res1 || d->res2)))) return C2M_ERR_UNSUPPORTED;
   if (wino && ((d->out_mode != 0 && d->out_mode != 3 && d->out_mode != 4) || d->Cout % 64 != 0 || d->W % 32 != 0)) return C2M_ERR_UNSUPPORTED;
   if (d->out_mode == 4 && !splitk && (d->algo != C2M_CONV_WINOGRAD_F23X || d->H % 2 != 0 || d->res1 || d->res2 || d->out2)) return C2M_ERR_UNSUPPORTED;
@@ -1641,7 +1674,8 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   }
   if (splitk) {
     ProfileScope prof(C2M_KERNEL_CONV3X3_SPLIT, as_stream(stream));
-    return conv::launch_split(as_stream(stream), p, d->algo == C2M_CONV_BF16 ? 1 : (d->algo == C2M_CONV_SPLIT_F16X2 ? 2 : 3));
+    return conv::launch_split(as_stream(stream), p, d->algo == C2M_CONV_BF16 ? 1 : (d->algo == C2M_CONV_SPLIT_F16X2 ? 2 : 3),
+                              roi_tiles_y, roi_tiles_x);
   }
   // 512 resident workgroups (2 per CU; the F(4,3) kernel: 256, 1 per CU), at most 10 tiles each
   const int ncb = ceil_div(d->Cout, MW);
@@ -1667,4 +1701,11 @@ extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc*
   if (rc != C2M_OK) return rc;
   hipLaunchKernelGGL(k.fn, grid, dim3(256), lds, st, p);
   return check_launch();
+}
+
+extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d) { return conv3x3_nhwc_launch(stream, d, 0, 0); }
+
+extern "C" int c2m_conv3x3_nhwc_roi_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d, int roi_tiles_y, int roi_tiles_x) {
+  if (roi_tiles_y <= 0 || roi_tiles_x <= 0) return C2M_ERR_INVALID_ARG;
+  return conv3x3_nhwc_launch(stream, d, roi_tiles_y, roi_tiles_x);
 }

@@ -51,6 +51,10 @@ struct Params {
 // MW = 32 * MT output channels (weight images are laid out for that MT: the re-layouts use the same rule).
 inline int cout_tiles(int Cout) { return Cout <= 32 ? 1 : 2; }
 
+// Pixel tile of a split-kernel workgroup (conv3x3_split.hip asserts its own TWX x THY against these): what the host code
+// reports through c2m_conv3x3_roi_tile.
+constexpr int kSplitTileW = 32, kSplitTileH = 8;
+
 // Tiles per workgroup: long streams amortise the set-up and the first DMA wait, but the launch is only as fast as its last
 // round of `resident` workgroups: take the tpw <= tmax with the fewest "rounds x tiles" (ties: the longer stream), e.g. at
 // 512 resident, tmax 10: 51200 tiles -> 10 (10 full rounds), 12800 -> 5 (5 full rounds).  $C2M_CONV_TPW overrides.

@@ -59,6 +59,7 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int KC = 16;                          // input channels per chunk = K of v_mfma_f32_32x32x16_bf16
 constexpr int TWX = 32, THY = 8;                // pixel tile of a workgroup
 constexpr int HWc = TWX + 2, HHr = THY + 2;     // halo tile 34 x 10
+static_assert(TWX == kSplitTileW && THY == kSplitTileH, "c2m_conv3x3_roi_tile reports the split kernels' tile");
 constexpr int NPIX = HWc * HHr;                 // 340
 constexpr int NRAW_W = (NPIX * 4 + 255) / 256;  // 6 loads per wave: 64 pieces of 16 B = (pixel, 4 fp32 channels).  4 waves x 6 = 24
                                                 // slots (22 carry pixels; the rest read zeros) -- every wave runs the same
@@ -1089,10 +1090,17 @@ static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid, int MT)
   return rc;
 }
 
-// p: as filled by c2m_conv3x3_nhwc_f32 (tiles / nchunks / tpw are set here)
-int launch_split(hipStream_t st, Params p, int np) {
+// p: as filled by c2m_conv3x3_nhwc_f32 (tiles / nchunks / tpw are set here).  roi_tiles_y / roi_tiles_x > 0: the tile grid
+// covers only the top-left roi_tiles_y x roi_tiles_x tiles (c2m_conv3x3_nhwc_roi_f32); the kernel decodes its tile from
+// Params::tiles_x / tiles_y and takes every address and bound from H / W, so those tiles come out as in the full launch.
+int launch_split(hipStream_t st, Params p, int np, int roi_tiles_y, int roi_tiles_x) {
   p.tiles_x = ceil_div(p.W, split::TWX);
   p.tiles_y = ceil_div(p.H, split::THY);
+  if (roi_tiles_y > 0 && roi_tiles_x > 0) {
+    if (roi_tiles_y > p.tiles_y || roi_tiles_x > p.tiles_x) return C2M_ERR_INVALID_ARG;
+    p.tiles_y = roi_tiles_y;
+    p.tiles_x = roi_tiles_x;
+  }
   p.nchunks = p.Cin / split::KC;
   const int MT = cout_tiles(p.Cout), ncb = ceil_div(p.Cout, 32 * MT);
   const long long ntile = (long long)p.tiles_x * p.tiles_y * p.B;

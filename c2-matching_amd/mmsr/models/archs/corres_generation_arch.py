@@ -93,6 +93,9 @@ class CorrespondenceGenerationArch(nn.Module):
         # these taps are warped by DCNv2, they do not feed the index search: their convolutions may run on the split-bf16
         # kernel (fp32-accurate on the bf16 matrix pipe, c2m_amd.ops.conv3x3(fast=True)) like the decoder's
         self.vgg.fast_conv = True
+        # img_ref_hr is the zero-padded Ref: the taps' convolutions launch only the tiles its live region reaches and fill the
+        # padding band from a template (c2m_amd.ops._RefBand; the extent is shared with the extractor's Ref tower of the step)
+        self.vgg.ref_band = True
 
     def index_to_flow(self, max_idx):
         """(h, w) int64 index map of ONE sample -> [1, h+2, w+2, 2] flow (x, y), zero-padded bottom/right

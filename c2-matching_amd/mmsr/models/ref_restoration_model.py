@@ -272,6 +272,10 @@ class RefRestorationModel(BaseModel):
         self.net_g.eval()
         with torch.no_grad():
             def whole():
+                if self.img_ref.is_cuda:
+                    # read the Ref's live extent while the queue is still empty; extractor and VGG taps share it
+                    from c2m_amd import ops as _ops
+                    _ops.ref_live_extent_shared(self.img_ref)
                 self._correspondence()
                 return self.net_g(self.img_in_lq, self.pre_offset, self.img_ref_feat)
             if self.img_in_lq.is_cuda:

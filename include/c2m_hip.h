@@ -349,6 +349,13 @@ int c2m_conv3x3_relayout_split_f32(c2m_stream_t stream, const float* weight, int
  * pieces = 2 (then one more launch reduces max |w| of those tensors for their scales). */
 int c2m_conv3x3_relayout_split_multi(c2m_stream_t stream, const long long* jobs, int njobs, long long nblocks, int any_f16);
 int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* desc);
+/* The same launch on the top-left roi_tiles_y x roi_tiles_x pixel tiles only (both > 0, at most the grid of the full launch;
+ * tile shape: c2m_conv3x3_roi_tile).  H, W, the sources and the outputs are those of the full launch: halos are read from the
+ * full-size input, the tiles computed come out bit for bit as c2m_conv3x3_nhwc_f32 writes them, everything else is left
+ * untouched (C2M_OUT_NHWC_POOL2: the pooled pixels of those tiles).  Split algorithms only, else C2M_ERR_UNSUPPORTED. */
+int c2m_conv3x3_nhwc_roi_f32(c2m_stream_t stream, const c2m_conv3x3_desc* desc, int roi_tiles_y, int roi_tiles_x);
+/* Pixel tile of a workgroup: of c2m_conv3x3_rgb64_f32 (rgb64 != 0) or of the split algorithms of c2m_conv3x3_nhwc_f32. */
+int c2m_conv3x3_roi_tile(int rgb64, int* tile_h, int* tile_w);
 
 /*
  * Backward of the same convolution (stage-3 training, ref_restoration_model.py:192-269; the reference leaves it to cuDNN).
@@ -379,6 +386,28 @@ int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H,
                           const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
                           int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2, int out2_row_pitch,
                           long long out2_plane_pitch, long long out2_img_pitch);
+/* ... on the top-left roi_tiles_y x roi_tiles_x tiles only (see c2m_conv3x3_nhwc_roi_f32). */
+int c2m_conv3x3_rgb64_roi_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
+                              const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
+                              int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2, int out2_row_pitch,
+                              long long out2_plane_pitch, long long out2_img_pitch, int roi_tiles_y, int roi_tiles_x);
+
+/*
+ * The padding band of a zero-padded Ref image (csrc/ref_band.hip).
+ * c2m_ref_live_extent_f32: image [B][3][H][W] planar fp32 -> extent[0] = 1 + the largest row index, extent[1] = 1 + the largest
+ *   column index of an element that is not exactly 0.0, over channels and batch.  `extent`: two DEVICE ints the caller has
+ *   zeroed (the kernel takes maxima into them).  3 B H W < 2^31 elements, else C2M_ERR_UNSUPPORTED.
+ * c2m_band_fill_f32: dst(b, c, y, x) = tmpl(c, s(y), s(x)) for every pixel outside [0, roi_h) x [0, roi_w), where s is the
+ *   edge-distance clamp: v < margin -> v; N - v <= margin -> T - (N - v); else margin (N = H / W, T = Ht / Wt, all of them
+ *   >= 2 margin + 1, else C2M_ERR_INVALID_ARG).  planar == 0: element (b, c, y, x) of dst at b*d_img + (c / cpg)*d_plane +
+ *   y*d_row + x*d_pix + c % cpg floats, of the one-sample template likewise with the t_ pitches (channels-last tensors and
+ *   views: cpg = C; the 8-channel group-major twin: cpg = 8); 16-byte aligned bases, pitches multiples of 4.  planar != 0:
+ *   contiguous [B][C][H][W] / [C][Ht][Wt] (the pitch arguments are ignored), W % 4 == 0 and roi_w % 4 == 0.
+ */
+int c2m_ref_live_extent_f32(c2m_stream_t stream, const float* image, int B, int H, int W, int* extent);
+int c2m_band_fill_f32(c2m_stream_t stream, float* dst, int B, int C, int H, int W, int cpg, int d_pix_pitch, int d_row_pitch,
+                      long long d_plane_pitch, long long d_img_pitch, const float* tmpl, int Ht, int Wt, int t_pix_pitch,
+                      int t_row_pitch, long long t_plane_pitch, int roi_h, int roi_w, int margin_y, int margin_x, int planar);
 
 /* max_idx [B][hq][wq] int64 -> flow [B][hq][wq][2] fp32 (x, y) = (idx % wq - x, idx / wq - y): index_to_flow of
  * corres_generation_arch.py:29-46 for the whole batch, without the zero padding (the consumer bounds-checks). */
