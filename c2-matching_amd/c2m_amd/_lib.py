@@ -12,9 +12,9 @@ import torch  # noqa: F401  (loads libamdhip64 before our library resolves it)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ($C2M_LIB: another build of the same library -- kernel A/B measurements; the product path is the in-tree build)
 LIB_PATH = os.environ.get("C2M_LIB") or os.path.join(os.path.dirname(_HERE), "csrc", "libc2m_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
-_vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+_vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 _lib = None
 
 
@@ -31,7 +31,27 @@ class Conv3x3Desc(ctypes.Structure):
                 ("res2", _vp), ("mask_out", _vp), ("flow", _vp), ("fh", _i), ("fw", _i), ("scale", _i), ("n_off", _i),
                 ("abs_sum", _vp), ("algo", _i), ("cout_offset", _i), ("cout_total", _i),
                 ("out2", _vp), ("out2_row_pitch", _i), ("out2_plane_pitch", ctypes.c_longlong),
-                ("out2_img_pitch", ctypes.c_longlong), ("range_flag", _vp), ("io_flags", ctypes.c_int)]
+                ("out2_img_pitch", ctypes.c_longlong), ("range_flag", _vp), ("io_flags", ctypes.c_int),
+                ("roi_tiles_y", _i), ("roi_tiles_x", _i)]
+
+
+class Conv3x3Rgb64Desc(ctypes.Structure):
+    """c2m_conv3x3_rgb64_desc of include/c2m_hip.h"""
+    _fields_ = [("image", _vp), ("B", _i), ("H", _i), ("W", _i), ("weight", _vp), ("bias", _vp), ("mean", _vp), ("std_", _vp),
+                ("act", _i), ("slope", ctypes.c_float), ("out", _vp), ("out_pix_pitch", _i), ("out_row_pitch", _i),
+                ("out_img_pitch", _ll), ("out2", _vp), ("out2_row_pitch", _i), ("out2_plane_pitch", _ll),
+                ("out2_img_pitch", _ll), ("roi_tiles_y", _i), ("roi_tiles_x", _i)]
+
+
+DCN_FP32, DCN_F16X2 = 0, 1   # c2m_dcn_nhwc_desc.arith
+
+
+class DcnNhwcDesc(ctypes.Structure):
+    """c2m_dcn_nhwc_desc of include/c2m_hip.h"""
+    _fields_ = [(n, _i) for n in ("B", "C", "H", "W", "Co", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "dg")] + [
+        ("input_bordered", _vp), ("input_grouped", _i), ("wt", _vp), ("bias", _vp), ("offset", _vp), ("mask", _vp),
+        ("output", _vp), ("out_nhwc", _i), ("out_pix_pitch", _i), ("out_row_pitch", _i), ("out_img_pitch", _ll),
+        ("act", _i), ("slope", ctypes.c_float), ("arith", _i), ("range_flag", _vp)]
 
 
 class ImageSrc(ctypes.Structure):
@@ -78,13 +98,11 @@ def _declare(L):
     L.c2m_dcn_v2_relayout_bytes.restype = _sz
     L.c2m_dcn_v2_relayout_bytes.argtypes = [_i] * 5
     L.c2m_dcn_v2_relayout_f32.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _vp]
-    L.c2m_conv3x3_rgb64_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_float, _vp, _i, _i,
-                                        ctypes.c_longlong, _vp, _i, ctypes.c_longlong, ctypes.c_longlong]
-    L.c2m_dcn_v2_forward_nhwc_f32.argtypes = [_vp] * 6 + [_i] * 14 + [_vp, _i, _i, _i, ctypes.c_longlong, _i, ctypes.c_float, _i]
+    L.c2m_conv3x3_rgb64_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Rgb64Desc)]
+    L.c2m_dcn_v2_forward_nhwc.argtypes = [_vp, ctypes.POINTER(DcnNhwcDesc)]
     L.c2m_dcn_v2_relayout_f16x2_bytes.restype = _sz
     L.c2m_dcn_v2_relayout_f16x2_bytes.argtypes = [_i] * 5
     L.c2m_dcn_v2_relayout_f16x2.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _vp]
-    L.c2m_dcn_v2_forward_nhwc_f16x2.argtypes = [_vp] * 6 + [_i] * 14 + [_vp, _i, _i, _i, ctypes.c_longlong, _i, ctypes.c_float, _i, _vp]
     L.c2m_conv3x3_relayout_bytes.restype = _sz
     L.c2m_conv3x3_relayout_bytes.argtypes = [_i, _i]
     L.c2m_conv3x3_relayout_f32.argtypes = [_vp, _vp, _i, _i, _vp]
@@ -103,11 +121,8 @@ def _declare(L):
     L.c2m_conv3x3_wgrad_workspace_bytes.argtypes = [_i] * 5
     L.c2m_conv3x3_wgrad_f32.argtypes = [_vp, ctypes.POINTER(ConvSrc), _i, _vp, _i, _i, ctypes.c_longlong] + [_i] * 5 + [_vp, _vp, _sz]
     L.c2m_conv3x3_nhwc_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Desc)]
-    L.c2m_conv3x3_nhwc_roi_f32.argtypes = [_vp, ctypes.POINTER(Conv3x3Desc), _i, _i]
-    L.c2m_conv3x3_rgb64_roi_f32.argtypes = L.c2m_conv3x3_rgb64_f32.argtypes + [_i, _i]
     L.c2m_conv3x3_roi_tile.argtypes = [_i, ctypes.POINTER(_i), ctypes.POINTER(_i)]
     L.c2m_ref_live_extent_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp]
-    _ll = ctypes.c_longlong
     L.c2m_band_fill_f32.argtypes = [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _ll, _vp, _i, _i, _i, _i, _ll] + [_i] * 5
     L.c2m_index_to_flow_f32.argtypes = [_vp, _vp, _i, _i, _i, _vp]
     L.c2m_contras_loss_workspace_bytes.restype = _sz

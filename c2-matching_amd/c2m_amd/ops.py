@@ -778,14 +778,12 @@ def _roi_pixels(roi_tiles, H, W, rgb64=False):
 
 
 def _launch_conv(d, dev, kind, family_prefix="", roi_tiles=None):
-    """c2m_conv3x3_nhwc_f32 (roi_tiles: c2m_conv3x3_nhwc_roi_f32, the top-left (tile rows, tile columns) only) on the current
-    stream of `dev` (+ the opt-in flop accounting of the launch: the pixels of the tiles actually launched)."""
+    """c2m_conv3x3_nhwc_f32 (roi_tiles: the top-left (tile rows, tile columns) only) on the current stream of `dev` (+ the
+    opt-in flop accounting of the launch: the pixels of the tiles actually launched)."""
+    if roi_tiles is not None:
+        d.roi_tiles_y, d.roi_tiles_x = int(roi_tiles[0]), int(roi_tiles[1])
     with torch.cuda.device(dev):
-        if roi_tiles is None:
-            _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
-        else:
-            _lib.check(_lib.lib().c2m_conv3x3_nhwc_roi_f32(_stream(), d, int(roi_tiles[0]), int(roi_tiles[1])),
-                       "c2m_conv3x3_nhwc_roi_f32")
+        _lib.check(_lib.lib().c2m_conv3x3_nhwc_f32(_stream(), d), "c2m_conv3x3_nhwc_f32")
     if _ConvFlops.enabled:
         rh, rw = _roi_pixels(roi_tiles, d.H, d.W)
         f = 2.0 * d.Cout * 9 * d.Cin * rh * rw * d.B
@@ -1043,15 +1041,15 @@ def conv3x3_rgb64(image, weight, bias=None, act=ACT_NONE, slope=0.1, mean=None, 
     if tuple(out.shape) != (B, 64, H, W):
         raise _lib.C2MError("conv3x3_rgb64: out must be [B,64,H,W]")
     o2, o2_row, o2_plane, o2_img = _grouped8_args(out2_grouped8, B, 64, H, W, dev)
-    args = (x.data_ptr(), B, H, W, w.data_ptr(), bias.data_ptr() if bias is not None else None,
-            mean.data_ptr() if mean is not None else None, std.data_ptr() if std is not None else None, int(act),
-            float(slope), out.data_ptr(), o.pix_pitch, o.row_pitch, o.img_pitch, o2, o2_row, o2_plane, o2_img)
+    d = _lib.Conv3x3Rgb64Desc(
+        image=x.data_ptr(), B=B, H=H, W=W, weight=w.data_ptr(), bias=bias.data_ptr() if bias is not None else None,
+        mean=mean.data_ptr() if mean is not None else None, std_=std.data_ptr() if std is not None else None, act=int(act),
+        slope=float(slope), out=out.data_ptr(), out_pix_pitch=o.pix_pitch, out_row_pitch=o.row_pitch, out_img_pitch=o.img_pitch,
+        out2=o2, out2_row_pitch=o2_row, out2_plane_pitch=o2_plane, out2_img_pitch=o2_img)
+    if roi_tiles is not None:
+        d.roi_tiles_y, d.roi_tiles_x = int(roi_tiles[0]), int(roi_tiles[1])
     with torch.cuda.device(dev):
-        if roi_tiles is None:
-            _lib.check(_lib.lib().c2m_conv3x3_rgb64_f32(_stream(), *args), "c2m_conv3x3_rgb64_f32")
-        else:
-            _lib.check(_lib.lib().c2m_conv3x3_rgb64_roi_f32(_stream(), *args, int(roi_tiles[0]), int(roi_tiles[1])),
-                       "c2m_conv3x3_rgb64_roi_f32")
+        _lib.check(_lib.lib().c2m_conv3x3_rgb64_f32(_stream(), d), "c2m_conv3x3_rgb64_f32")
     if _ConvFlops.enabled:
         rh, rw = _roi_pixels(roi_tiles, H, W, rgb64=True)
         _ConvFlops.add("rgb_first_layer", 2.0 * 64 * 27 * rh * rw * B, 2.0 * 64 * 28 * rh * rw * B)
@@ -1240,21 +1238,22 @@ def dcn_v2_forward_nhwc(inp_bordered, weight, bias, offset, mask, deformable_gro
         raise _lib.C2MError("dcn_v2_forward_nhwc: algo is None, 'fp32' or 'f16x2'")
     wt = _dcn_wcache.get(weight, dg, f16x2=f16)
     dev = offset.device
+    grouped = inp_bordered.grouped8 is not None and C == 8 * dg
+    src = inp_bordered.grouped8 if grouped else inp_bordered.buf
+    d = _lib.DcnNhwcDesc(B=B, C=C, H=H, W=W, Co=Co, kh=3, kw=3, sh=1, sw=1, ph=1, pw=1, dh=1, dw=1, dg=dg,
+                         input_bordered=src.data_ptr(), input_grouped=int(grouped), wt=wt.data_ptr(), bias=bias.data_ptr(),
+                         offset=offset.data_ptr(), mask=mask.data_ptr(), act=int(act), slope=float(slope))
     if nhwc_out:
         out = empty_nhwc(B, Co, H, W, dev)
         o = _nhwc_src(out, "out")
-        pitches = (1, o.pix_pitch, o.row_pitch, o.img_pitch)
+        d.out_nhwc, d.out_pix_pitch, d.out_row_pitch, d.out_img_pitch = 1, o.pix_pitch, o.row_pitch, o.img_pitch
     else:
         out = torch.empty((B, Co, H, W), dtype=torch.float32, device=dev)
-        pitches = (0, 0, 0, 0)
-    grouped = inp_bordered.grouped8 is not None and C == 8 * dg
-    src = inp_bordered.grouped8 if grouped else inp_bordered.buf
-    fn = "c2m_dcn_v2_forward_nhwc_f16x2" if f16 else "c2m_dcn_v2_forward_nhwc_f32"
+    d.output = out.data_ptr()
     with torch.cuda.device(dev):
-        tail = (_range_flag(dev).data_ptr(),) if f16 else ()   # the f16 x 2 entry point takes the range flag last
-        _lib.check(getattr(_lib.lib(), fn)(_stream(), src.data_ptr(), wt.data_ptr(), bias.data_ptr(), offset.data_ptr(),
-                                           mask.data_ptr(), B, C, H, W, Co, 3, 3, 1, 1, 1, 1, 1, 1, dg, out.data_ptr(), *pitches,
-                                           int(act), float(slope), int(grouped), *tail), fn)
+        if f16:
+            d.arith, d.range_flag = _lib.DCN_F16X2, _range_flag(dev).data_ptr()
+        _lib.check(_lib.lib().c2m_dcn_v2_forward_nhwc(_stream(), d), "c2m_dcn_v2_forward_nhwc")
     return out
 
 

@@ -1509,63 +1509,49 @@ extern "C" int c2m_conv3x3_relayout_wino_f32(c2m_stream_t stream, const float* w
   return check_launch();
 }
 
-// roi_tiles_y / roi_tiles_x > 0: only the top-left tiles of the grid (c2m_conv3x3_rgb64_roi_f32)
-static int conv3x3_rgb64_launch(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                                const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
-                                int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
-                                int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch, int roi_tiles_y,
-                                int roi_tiles_x) {
-  if (!image || !weight || !out || B <= 0 || H <= 0 || W <= 0 || (mean == nullptr) != (std_ == nullptr)) return C2M_ERR_INVALID_ARG;
-  if (act < 0 || act > 2 || (act == C2M_ACT_LEAKY_RELU && !(slope >= 0.0f && slope <= 1.0f))) return C2M_ERR_UNSUPPORTED;
-  if (out_pix_pitch % 4 != 0 || out_row_pitch % 4 != 0 || out_img_pitch % 4 != 0 || ((uintptr_t)out & 15)) return C2M_ERR_UNSUPPORTED;
-  if (out2 && (out2_row_pitch % 4 != 0 || out2_plane_pitch % 4 != 0 || out2_img_pitch % 4 != 0 || ((uintptr_t)out2 & 15)))
+// the ROI of both descriptors: both 0 (the whole grid) or both > 0 (the top-left tiles)
+static bool roi_ok(int roi_tiles_y, int roi_tiles_x) {
+  return (roi_tiles_y == 0 && roi_tiles_x == 0) || (roi_tiles_y > 0 && roi_tiles_x > 0);
+}
+
+extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const c2m_conv3x3_rgb64_desc* d) {
+  if (!d || !d->image || !d->weight || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || (d->mean == nullptr) != (d->std_ == nullptr) ||
+      !roi_ok(d->roi_tiles_y, d->roi_tiles_x))
+    return C2M_ERR_INVALID_ARG;
+  const int act = d->act;
+  if (act < 0 || act > 2 || (act == C2M_ACT_LEAKY_RELU && !(d->slope >= 0.0f && d->slope <= 1.0f))) return C2M_ERR_UNSUPPORTED;
+  if (d->out_pix_pitch % 4 != 0 || d->out_row_pitch % 4 != 0 || d->out_img_pitch % 4 != 0 || ((uintptr_t)d->out & 15)) return C2M_ERR_UNSUPPORTED;
+  if (d->out2 && (d->out2_row_pitch % 4 != 0 || d->out2_plane_pitch % 4 != 0 || d->out2_img_pitch % 4 != 0 || ((uintptr_t)d->out2 & 15)))
     return C2M_ERR_UNSUPPORTED;
   conv::c3::Params p;
-  p.in = image; p.w = weight; p.bias = bias; p.mean = mean; p.std_ = std_;
-  p.B = B; p.H = H; p.W = W;
-  p.tiles_x = ceil_div(W, conv::c3::CTW); p.tiles_y = ceil_div(H, conv::c3::CTH);
-  if (roi_tiles_y > 0 && roi_tiles_x > 0) {
-    if (roi_tiles_y > p.tiles_y || roi_tiles_x > p.tiles_x) return C2M_ERR_INVALID_ARG;
-    p.tiles_y = roi_tiles_y; p.tiles_x = roi_tiles_x;
+  p.in = d->image; p.w = d->weight; p.bias = d->bias; p.mean = d->mean; p.std_ = d->std_;
+  p.B = d->B; p.H = d->H; p.W = d->W;
+  p.tiles_x = ceil_div(d->W, conv::c3::CTW); p.tiles_y = ceil_div(d->H, conv::c3::CTH);
+  if (d->roi_tiles_y > 0) {
+    if (d->roi_tiles_y > p.tiles_y || d->roi_tiles_x > p.tiles_x) return C2M_ERR_INVALID_ARG;
+    p.tiles_y = d->roi_tiles_y; p.tiles_x = d->roi_tiles_x;
   }
-  p.act = act; p.slope = slope; p.out = out; p.out_pix_pitch = out_pix_pitch; p.out_row_pitch = out_row_pitch;
-  p.out_img_pitch = out_img_pitch; p.out2 = out2; p.out2_row_pitch = out2_row_pitch; p.out2_plane_pitch = out2_plane_pitch;
-  p.out2_img_pitch = out2_img_pitch;
-  const long long ntile = (long long)p.tiles_x * p.tiles_y * B;
+  p.act = act; p.slope = d->slope; p.out = d->out; p.out_pix_pitch = d->out_pix_pitch; p.out_row_pitch = d->out_row_pitch;
+  p.out_img_pitch = d->out_img_pitch; p.out2 = d->out2; p.out2_row_pitch = d->out2_row_pitch;
+  p.out2_plane_pitch = d->out2_plane_pitch; p.out2_img_pitch = d->out2_img_pitch;
+  const long long ntile = (long long)p.tiles_x * p.tiles_y * d->B;
   if (ntile > 0x7fffffffLL) return C2M_ERR_INVALID_ARG;
   // buffer addressing inside one image (loads) / one row of tiles (stores): every byte offset, and bit 31 as the "outside" mark,
   // must fit 32 bits
-  const long long in_b = 12LL * H * W,
-                  out_b = 4LL * ((long long)(conv::c3::CTH - 1) * out_row_pitch + (long long)(W - 1) * out_pix_pitch + 64),
-                  out2_b = out2 ? 4LL * ((long long)(conv::c3::CTH - 1) * out2_row_pitch + 8LL * W) : 0;
-  if (in_b >= (1LL << 31) || out_b >= (1LL << 31) || out2_b >= (1LL << 31) || out_row_pitch < 0 || out_pix_pitch < 0) return C2M_ERR_UNSUPPORTED;
+  const long long in_b = 12LL * d->H * d->W,
+                  out_b = 4LL * ((long long)(conv::c3::CTH - 1) * d->out_row_pitch + (long long)(d->W - 1) * d->out_pix_pitch + 64),
+                  out2_b = d->out2 ? 4LL * ((long long)(conv::c3::CTH - 1) * d->out2_row_pitch + 8LL * d->W) : 0;
+  if (in_b >= (1LL << 31) || out_b >= (1LL << 31) || out2_b >= (1LL << 31) || d->out_row_pitch < 0 || d->out_pix_pitch < 0)
+    return C2M_ERR_UNSUPPORTED;
   p.out_bytes = (unsigned)out_b; p.out2_bytes = (unsigned)out2_b;
   hipStream_t st = as_stream(stream);
   ProfileScope prof(C2M_KERNEL_CONV3X3, st);
   // persistent workgroups (the weights stay in registers): 3 fit a CU (164 VGPRs), tiles strided over them
   void (*kern)(conv::c3::Params) =
-      out2 ? (act == 0 ? &conv::conv3x3_c3_kernel<0, true> : act == 1 ? &conv::conv3x3_c3_kernel<1, true> : &conv::conv3x3_c3_kernel<2, true>)
-           : (act == 0 ? &conv::conv3x3_c3_kernel<0, false> : act == 1 ? &conv::conv3x3_c3_kernel<1, false> : &conv::conv3x3_c3_kernel<2, false>);
+      d->out2 ? (act == 0 ? &conv::conv3x3_c3_kernel<0, true> : act == 1 ? &conv::conv3x3_c3_kernel<1, true> : &conv::conv3x3_c3_kernel<2, true>)
+              : (act == 0 ? &conv::conv3x3_c3_kernel<0, false> : act == 1 ? &conv::conv3x3_c3_kernel<1, false> : &conv::conv3x3_c3_kernel<2, false>);
   hipLaunchKernelGGL(kern, dim3((unsigned)std::min<long long>(ntile, 768)), dim3(256), 0, st, p);
   return check_launch();
-}
-
-extern "C" int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                                     const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
-                                     int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
-                                     int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch) {
-  return conv3x3_rgb64_launch(stream, image, B, H, W, weight, bias, mean, std_, act, slope, out, out_pix_pitch, out_row_pitch,
-                              out_img_pitch, out2, out2_row_pitch, out2_plane_pitch, out2_img_pitch, 0, 0);
-}
-
-extern "C" int c2m_conv3x3_rgb64_roi_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                                         const float* bias, const float* mean, const float* std_, int act, float slope,
-                                         float* out, int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2,
-                                         int out2_row_pitch, long long out2_plane_pitch, long long out2_img_pitch,
-                                         int roi_tiles_y, int roi_tiles_x) {
-  if (roi_tiles_y <= 0 || roi_tiles_x <= 0) return C2M_ERR_INVALID_ARG;
-  return conv3x3_rgb64_launch(stream, image, B, H, W, weight, bias, mean, std_, act, slope, out, out_pix_pitch, out_row_pitch,
-                              out_img_pitch, out2, out2_row_pitch, out2_plane_pitch, out2_img_pitch, roi_tiles_y, roi_tiles_x);
 }
 
 extern "C" int c2m_conv3x3_roi_tile(int rgb64, int* tile_h, int* tile_w) {
@@ -1583,16 +1569,15 @@ extern "C" int c2m_index_to_flow_f32(c2m_stream_t stream, const int64_t* max_idx
   return check_launch();
 }
 
-// roi_tiles_y / roi_tiles_x > 0: only the top-left tiles of the grid, split kernels only (c2m_conv3x3_nhwc_roi_f32)
-static int conv3x3_nhwc_launch(c2m_stream_t stream, const c2m_conv3x3_desc* d, int roi_tiles_y, int roi_tiles_x) {
+extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d) {
   if (!d || !d->wr || !d->out || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->nsrc < 1 ||
-      d->nsrc > 2 || !d->src[0].ptr || (d->nsrc == 2 && !d->src[1].ptr))
+      d->nsrc > 2 || !d->src[0].ptr || (d->nsrc == 2 && !d->src[1].ptr) || !roi_ok(d->roi_tiles_y, d->roi_tiles_x))
     return C2M_ERR_INVALID_ARG;
   const bool wino4 = d->algo == C2M_CONV_WINOGRAD_F43X;
   const bool wino = d->algo == C2M_CONV_WINOGRAD_F23X || wino4;   // both: 16-channel chunks, 64-cout blocks
   const bool splitk = d->algo == C2M_CONV_SPLIT_BF16X3 || d->algo == C2M_CONV_BF16 || d->algo == C2M_CONV_SPLIT_F16X2;   // 16-channel chunks, any shape
   if (d->algo != 0 && !wino && !splitk) return C2M_ERR_INVALID_ARG;
-  if (roi_tiles_y > 0 && !splitk) return C2M_ERR_UNSUPPORTED;
+  if (d->roi_tiles_y > 0 && !splitk) return C2M_ERR_UNSUPPORTED;   // the ROI launches the split kernels only
   if (splitk && (d->out2 || (d->out_mode == 4 && (d->H % 2 != 0 || d->W % 2 != 0 || d->res1 || d->res2)))) return C2M_ERR_UNSUPPORTED;
   if (wino && ((d->out_mode != 0 && d->out_mode != 3 && d->out_mode != 4) || d->Cout % 64 != 0 || d->W % 32 != 0)) return C2M_ERR_UNSUPPORTED;
   if (d->out_mode == 4 && !splitk && (d->algo != C2M_CONV_WINOGRAD_F23X || d->H % 2 != 0 || d->res1 || d->res2 || d->out2)) return C2M_ERR_UNSUPPORTED;
@@ -1675,7 +1660,7 @@ static int conv3x3_nhwc_launch(c2m_stream_t stream, const c2m_conv3x3_desc* d, i
   if (splitk) {
     ProfileScope prof(C2M_KERNEL_CONV3X3_SPLIT, as_stream(stream));
     return conv::launch_split(as_stream(stream), p, d->algo == C2M_CONV_BF16 ? 1 : (d->algo == C2M_CONV_SPLIT_F16X2 ? 2 : 3),
-                              roi_tiles_y, roi_tiles_x);
+                              d->roi_tiles_y, d->roi_tiles_x);
   }
   // 512 resident workgroups (2 per CU; the F(4,3) kernel: 256, 1 per CU), at most 10 tiles each
   const int ncb = ceil_div(d->Cout, MW);
@@ -1701,11 +1686,4 @@ static int conv3x3_nhwc_launch(c2m_stream_t stream, const c2m_conv3x3_desc* d, i
   if (rc != C2M_OK) return rc;
   hipLaunchKernelGGL(k.fn, grid, dim3(256), lds, st, p);
   return check_launch();
-}
-
-extern "C" int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d) { return conv3x3_nhwc_launch(stream, d, 0, 0); }
-
-extern "C" int c2m_conv3x3_nhwc_roi_f32(c2m_stream_t stream, const c2m_conv3x3_desc* d, int roi_tiles_y, int roi_tiles_x) {
-  if (roi_tiles_y <= 0 || roi_tiles_x <= 0) return C2M_ERR_INVALID_ARG;
-  return conv3x3_nhwc_launch(stream, d, roi_tiles_y, roi_tiles_x);
 }

@@ -1091,7 +1091,7 @@ static int launch_split_mode(hipStream_t st, const Params& p, dim3 grid, int MT)
 }
 
 // p: as filled by c2m_conv3x3_nhwc_f32 (tiles / nchunks / tpw are set here).  roi_tiles_y / roi_tiles_x > 0: the tile grid
-// covers only the top-left roi_tiles_y x roi_tiles_x tiles (c2m_conv3x3_nhwc_roi_f32); the kernel decodes its tile from
+// covers only the top-left roi_tiles_y x roi_tiles_x tiles (c2m_conv3x3_desc::roi_tiles_y / roi_tiles_x); the kernel decodes its tile from
 // Params::tiles_x / tiles_y and takes every address and bound from H / W, so those tiles come out as in the full launch.
 int launch_split(hipStream_t st, Params p, int np, int roi_tiles_y, int roi_tiles_x) {
   p.tiles_x = ceil_div(p.W, split::TWX);

@@ -1396,7 +1396,7 @@ inline bool use_nhwc(const Geom& g) {
 // count.  (Measured, B=16: large layer 16.4 -> 13.7 ms on random flows, 7.6 -> 7.1 ms on coherent ones; 16-channel groups
 // lose 2-10 %, so they stay.)  The rule reads C and dg only, so the image made from the probe geometry (relayout_geom) is
 // the one the forward of any map size multiplies with: dcn_forward asks use_nhwc of the real geometry, the re-layout entry
-// points of the probe, and a forward that is handed an image (FwdExt::wt) on a geometry off the fast path is refused.
+// points of the probe, and a forward that is handed an image (c2m_dcn_nhwc_desc::wt) on a geometry off the fast path is refused.
 inline Geom kernel_geom(const Geom& g) {
   Geom gk = g;
   if (g.CPG == 8 && g.dg % 4 == 0) { gk.CPG = 2 * g.CPG; gk.dg = g.dg / 2; }
@@ -1511,56 +1511,48 @@ void launch_nhwc_copy(hipStream_t st, const float* input, int B, int C, int H, i
                        st, input, C, H, W, out);
 }
 
-// Options of the fused decoder path (c2m_dcn_v2_forward_nhwc_f32): the caller already holds the zero-bordered channels-last
-// copy (shared with the offset convolutions) and the re-laid-out weights (cached while the weights do not change).
-struct FwdExt {
-  const float* inl = nullptr;   // bordered channels-last input [B][H+3][W+3][C]; nullptr: made here from `input`
-  int in_grouped = 0;           // `inl` is group-major [B][dg][H+3][W+3][C/dg] instead (8-channel groups only)
-  const float* wt = nullptr;    // weights in the forward kernel's layout; nullptr: re-laid-out here from `weight`
-  int out_nhwc = 0, out_pix_pitch = 0, out_row_pitch = 0, act = 0;
-  long long out_img_pitch = 0;
-  float slope = 0.0f;
-  int f16x2 = 0;                // `wt` holds the f16 x 2 image (c2m_dcn_v2_relayout_f16x2): GEMM on the f16 matrix pipe
-  int* range_flag = nullptr;
-};
-
-int dcn_forward(c2m_stream_t stream, const float* input, const float* weight, const float* bias, const float* offset,
-                const float* mask, int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw,
-                int dh, int dw, int dg, float* output, void* workspace, size_t workspace_bytes, bool want_bf16,
-                const FwdExt& ext = FwdExt()) {
-  if ((!input && !ext.inl) || (!weight && !ext.wt) || !bias || !offset || !mask || !output) return C2M_ERR_INVALID_ARG;
+// Every forward entry point describes its call with a c2m_dcn_nhwc_desc.  The fused decoder path (c2m_dcn_v2_forward_nhwc) hands
+// over the caller's: it already holds the zero-bordered channels-last copy (shared with the offset convolutions) and the
+// re-laid-out weights (cached while the weights do not change).  The NCHW entry points fill one without them (nchw_desc) and
+// pass `input` / `weight` and a workspace: the copy and the image are then made here.
+int dcn_forward(c2m_stream_t stream, const c2m_dcn_nhwc_desc& d, const float* input, const float* weight, void* workspace,
+                size_t workspace_bytes, bool want_bf16) {
+  const float *inl_in = d.input_bordered, *wt_in = static_cast<const float*>(d.wt);
+  const int B = d.B, C = d.C, H = d.H, W = d.W, Co = d.Co;
+  const bool f16x2 = d.arith == C2M_DCN_F16X2;
+  if ((!input && !inl_in) || (!weight && !wt_in) || !d.bias || !d.offset || !d.mask || !d.output) return C2M_ERR_INVALID_ARG;
   Geom g;
-  int rc = make_geom(g, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg);
+  int rc = make_geom(g, B, C, H, W, Co, d.kh, d.kw, d.sh, d.sw, d.ph, d.pw, d.dh, d.dw, d.dg);
   if (rc != C2M_OK) return rc;
   if (g.CPG % 2 != 0) return C2M_ERR_UNSUPPORTED;  // k-pairs of the fp32 MFMA never straddle a (group, tap)
   g.CoPad = copad_fwd(Co);
   const bool nhwc = use_nhwc(g);
-  if ((ext.inl || ext.wt || ext.out_nhwc) && (!nhwc || want_bf16)) return C2M_ERR_UNSUPPORTED;
-  if (ext.out_nhwc && (Co % 4 != 0 || ext.out_pix_pitch % 4 != 0 || ext.out_row_pitch % 4 != 0 || ext.out_img_pitch % 4 != 0 ||
-                       ((uintptr_t)output & 15)))
+  if ((inl_in || wt_in || d.out_nhwc) && (!nhwc || want_bf16)) return C2M_ERR_UNSUPPORTED;
+  if (d.out_nhwc && (Co % 4 != 0 || d.out_pix_pitch % 4 != 0 || d.out_row_pitch % 4 != 0 || d.out_img_pitch % 4 != 0 ||
+                     ((uintptr_t)d.output & 15)))
     return C2M_ERR_UNSUPPORTED;
-  g.out_nhwc = ext.out_nhwc; g.out_pix_pitch = ext.out_pix_pitch; g.out_row_pitch = ext.out_row_pitch;
-  g.out_img_pitch = ext.out_img_pitch; g.act = ext.act; g.slope = ext.slope;
-  g.range_flag = ext.range_flag;
-  const size_t wbytes = ext.wt ? 0 : align256(sizeof(float) * (size_t)g.KtotPad * g.CoPad);
-  const size_t need = wbytes + ((nhwc && !ext.inl) ? bordered_copy_bytes(B, C, H, W) : 0);
+  g.out_nhwc = d.out_nhwc; g.out_pix_pitch = d.out_pix_pitch; g.out_row_pitch = d.out_row_pitch;
+  g.out_img_pitch = d.out_img_pitch; g.act = d.act; g.slope = d.slope;
+  g.range_flag = f16x2 ? d.range_flag : nullptr;
+  const size_t wbytes = wt_in ? 0 : align256(sizeof(float) * (size_t)g.KtotPad * g.CoPad);
+  const size_t need = wbytes + ((nhwc && !inl_in) ? bordered_copy_bytes(B, C, H, W) : 0);
   if (need > 0 && (!workspace || workspace_bytes < need)) return C2M_ERR_WORKSPACE;
   // 8-channel groups gather from a group-major copy (see Geom::in_grouped); a caller-provided copy says which it is
-  if (ext.in_grouped && !(ext.inl && nhwc && g.CPG == 8)) return C2M_ERR_UNSUPPORTED;
-  g.in_grouped = (ext.inl ? ext.in_grouped != 0 : (nhwc && g.CPG == 8)) ? 1 : 0;
+  if (d.input_grouped && !(inl_in && nhwc && g.CPG == 8)) return C2M_ERR_UNSUPPORTED;
+  g.in_grouped = (inl_in ? d.input_grouped != 0 : (nhwc && g.CPG == 8)) ? 1 : 0;
   const Geom gk = nhwc ? kernel_geom(g) : g;
   const bool split = gk.dg != g.dg;
   // bf16 MFMA variant: channels-last geometries whose half-run is a multiple of 8 channels; anything else computes in fp32
   const bool bf16 = want_bf16 && nhwc && gk.CPG >= 16;
-  if (ext.f16x2 && (!ext.wt || !nhwc || gk.CPG < 16)) return C2M_ERR_UNSUPPORTED;
+  if (f16x2 && (!wt_in || !nhwc || gk.CPG < 16)) return C2M_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
-  float* wt = ext.wt ? const_cast<float*>(ext.wt) : static_cast<float*>(workspace);
-  float* inl = ext.inl ? const_cast<float*>(ext.inl) : reinterpret_cast<float*>(static_cast<char*>(workspace) + wbytes);
-  if (nhwc && !ext.inl) {
+  float* wt = wt_in ? const_cast<float*>(wt_in) : static_cast<float*>(workspace);
+  float* inl = inl_in ? const_cast<float*>(inl_in) : reinterpret_cast<float*>(static_cast<char*>(workspace) + wbytes);
+  if (nhwc && !inl_in) {
     if (bf16) launch_nhwc_copy(st, input, B, C, H, W, reinterpret_cast<__bf16*>(inl), g.in_grouped != 0);
     else launch_nhwc_copy(st, input, B, C, H, W, inl, g.in_grouped != 0);
   }
-  if (!ext.wt) {
+  if (!wt_in) {
     if (bf16)
       hipLaunchKernelGGL(dcn::weight_relayout_bf16_kernel, dim3(ceil_div(g.CoPad * g.Ktot, 256)), dim3(256), 0, st, weight, gk,
                          reinterpret_cast<__bf16*>(wt));
@@ -1569,11 +1561,11 @@ int dcn_forward(c2m_stream_t stream, const float* input, const float* weight, co
                          nhwc ? 1 : 0, wt, (float*)nullptr);
   }
   if ((rc = check_launch()) != C2M_OK) return rc;
-  const FwdArgs a = {st, nhwc ? inl : input, wt, bias, offset, mask, gk, output};
+  const FwdArgs a = {st, nhwc ? inl : input, wt, d.bias, d.offset, d.mask, gk, d.output};
   {
     ProfileScope prof(C2M_KERNEL_DCN_FWD, st);
     if (nhwc) {
-      rc = select_fwd_nhwc(a, ext.f16x2 ? F16X2 : bf16 ? BF16 : FP32, split);
+      rc = select_fwd_nhwc(a, f16x2 ? F16X2 : bf16 ? BF16 : FP32, split);
       if (rc != C2M_OK) return rc;
     } else {
       switch (fwd_mt(Co)) {
@@ -1587,14 +1579,12 @@ int dcn_forward(c2m_stream_t stream, const float* input, const float* weight, co
   return check_launch();
 }
 
-// the two channels-last entry points: the caller's bordered copy and weight image, output layout and activation
-FwdExt nhwc_ext(const float* input_bordered, int input_grouped, const void* wt, int out_nhwc, int out_pix_pitch,
-                int out_row_pitch, long long out_img_pitch, int act, float slope) {
-  FwdExt ext;
-  ext.inl = input_bordered; ext.in_grouped = input_grouped; ext.wt = static_cast<const float*>(wt); ext.out_nhwc = out_nhwc;
-  ext.out_pix_pitch = out_pix_pitch; ext.out_row_pitch = out_row_pitch; ext.out_img_pitch = out_img_pitch; ext.act = act;
-  ext.slope = slope;
-  return ext;
+// the descriptor of an NCHW entry point's call: planar fp32 output, no caller-made copy or weight image
+c2m_dcn_nhwc_desc nchw_desc(const float* bias, const float* offset, const float* mask, int B, int C, int H, int W, int Co, int kh,
+                            int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg, float* output) {
+  c2m_dcn_nhwc_desc d = {B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg};
+  d.bias = bias; d.offset = offset; d.mask = mask; d.output = output;
+  return d;
 }
 }  // namespace
 
@@ -1621,14 +1611,9 @@ extern "C" int c2m_dcn_v2_relayout_f32(c2m_stream_t stream, const float* weight,
   return check_launch();
 }
 
-extern "C" int c2m_dcn_v2_forward_nhwc_f32(c2m_stream_t stream, const float* input_bordered, const float* wt,
-                                           const float* bias, const float* offset, const float* mask, int B, int C, int H,
-                                           int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                                           int dg, float* output, int out_nhwc, int out_pix_pitch, int out_row_pitch,
-                                           long long out_img_pitch, int act, float slope, int input_grouped) {
-  const FwdExt ext = nhwc_ext(input_bordered, input_grouped, wt, out_nhwc, out_pix_pitch, out_row_pitch, out_img_pitch, act, slope);
-  return dcn_forward(stream, nullptr, nullptr, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
-                     nullptr, 0, false, ext);
+extern "C" int c2m_dcn_v2_forward_nhwc(c2m_stream_t stream, const c2m_dcn_nhwc_desc* d) {
+  if (!d || (d->arith != C2M_DCN_FP32 && d->arith != C2M_DCN_F16X2)) return C2M_ERR_INVALID_ARG;
+  return dcn_forward(stream, *d, nullptr, nullptr, nullptr, 0, false);
 }
 
 // ---- f16 x 2 GEMM (channels-last path, >= 16 channels per -- possibly virtual -- group)
@@ -1657,22 +1642,11 @@ extern "C" int c2m_dcn_v2_relayout_f16x2(c2m_stream_t stream, const float* weigh
   return check_launch();
 }
 
-extern "C" int c2m_dcn_v2_forward_nhwc_f16x2(c2m_stream_t stream, const float* input_bordered, const void* wt,
-                                             const float* bias, const float* offset, const float* mask, int B, int C, int H,
-                                             int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
-                                             int dg, float* output, int out_nhwc, int out_pix_pitch, int out_row_pitch,
-                                             long long out_img_pitch, int act, float slope, int input_grouped, int* range_flag) {
-  FwdExt ext = nhwc_ext(input_bordered, input_grouped, wt, out_nhwc, out_pix_pitch, out_row_pitch, out_img_pitch, act, slope);
-  ext.f16x2 = 1; ext.range_flag = range_flag;
-  return dcn_forward(stream, nullptr, nullptr, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
-                     nullptr, 0, false, ext);
-}
-
 extern "C" int c2m_dcn_v2_forward_f32(c2m_stream_t stream, const float* input, const float* weight, const float* bias,
                                       const float* offset, const float* mask, int B, int C, int H, int W, int Co, int kh,
                                       int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg, float* output,
                                       void* workspace, size_t workspace_bytes) {
-  return dcn_forward(stream, input, weight, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
+  return dcn_forward(stream, nchw_desc(bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output), input, weight,
                      workspace, workspace_bytes, false);
 }
 
@@ -1680,7 +1654,7 @@ extern "C" int c2m_dcn_v2_forward_bf16mma_f32(c2m_stream_t stream, const float* 
                                               const float* bias, const float* offset, const float* mask, int B, int C,
                                               int H, int W, int Co, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
                                               int dw, int dg, float* output, void* workspace, size_t workspace_bytes) {
-  return dcn_forward(stream, input, weight, bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output,
+  return dcn_forward(stream, nchw_desc(bias, offset, mask, B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg, output), input, weight,
                      workspace, workspace_bytes, true);
 }
 

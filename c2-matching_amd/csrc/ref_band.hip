@@ -4,7 +4,7 @@
 // Behind the live region plus the receptive radius of a layer, a feature map no longer depends on the image: its value at a
 // pixel is a function of that pixel's distances to the four canvas edges only (zero padding outside the canvas against
 // act(bias) propagated inside), and constant once all four exceed the radius.  The Ref-side towers therefore launch their
-// convolutions on the top-left tiles only (c2m_conv3x3_nhwc_roi_f32 / c2m_conv3x3_rgb64_roi_f32), run the same layers once on a
+// convolutions on the top-left tiles only (roi_tiles_y / roi_tiles_x of the two convolution descriptors), run the same layers once on a
 // small all-zero canvas (the TEMPLATE, B = 1), and copy the band from it:
 //
 //   c2m_ref_live_extent_f32   img [B][3][H][W] -> (live_h, live_w): 1 + the largest row / column index of a pixel that is not

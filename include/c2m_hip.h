@@ -43,7 +43,8 @@ typedef enum c2m_status {
   C2M_ERR_NO_DEVICE = 5      /* no gfx950 device visible to the HIP runtime */
 } c2m_status;
 
-int c2m_abi_version(void);                 /* bumped on any signature change; currently 5 (v5: the correlation takes a flags word, the two A/B setters removed) */
+int c2m_abi_version(void);                 /* bumped on any signature change; currently 6 (v6: the fused DCNv2 forward and the first-layer
+                                              convolution take a descriptor each, the ROI is two descriptor fields) */
 const char* c2m_status_string(int status); /* static string, never NULL */
 const char* c2m_last_hip_error(void);      /* hipGetErrorString of the last failing HIP call on this thread */
 int c2m_device_arch(char* buf, int buflen);/* gcnArchName of the current device, e.g. "gfx950:sramecc+:xnack-" */
@@ -171,39 +172,43 @@ int c2m_dcn_v2_forward_bf16mma_f32(c2m_stream_t stream, const float* input, cons
  *   c2m_dcn_v2_relayout_f32         weight [Co][C][kh][kw] -> the kernel's A-operand layout (cache it while the weights
  *                                   do not change); c2m_dcn_v2_relayout_bytes == 0: geometry not on the channels-last path
  *                                   (8/16/32 channels per group and an even group count are).
- *   c2m_dcn_v2_forward_nhwc_f32     dcn_v2_cuda_forward (dcn_v2_cuda.cu:42-172) from those two; output planar
- *                                   [B][Co][Ho][Wo] (out_nhwc = 0) or channels-last with the given pitches (in floats)
- *                                   and an optional fused activation (C2M_ACT_*: the lrelu that follows every DynAgg,
- *                                   ref_restoration_arch.py:152-154).  input_grouped = 1 (C / dg == 8 only):
- *                                   input_bordered is group-major [B][dg][H+3][W+3][8] instead -- a 32-byte sample run
- *                                   then shares its 128-byte line with the neighbouring positions of the same group
- *                                   instead of with three other groups (c2m_conv3x3_desc.out2 writes this layout).
+ *   c2m_dcn_v2_forward_nhwc         dcn_v2_cuda_forward (dcn_v2_cuda.cu:42-172) from those two, described by a c2m_dcn_nhwc_desc
+ *                                   (zero-initialise it and set what the call needs, as for c2m_conv3x3_desc).
  */
 int c2m_nchw_to_nhwc_bordered_f32(c2m_stream_t stream, const float* input, int B, int C, int H, int W, float* out);
 size_t c2m_dcn_v2_relayout_bytes(int C, int Co, int kh, int kw, int dg);
 int c2m_dcn_v2_relayout_f32(c2m_stream_t stream, const float* weight, int C, int Co, int kh, int kw, int dg, float* wt);
-int c2m_dcn_v2_forward_nhwc_f32(c2m_stream_t stream, const float* input_bordered, const float* wt, const float* bias,
-                                const float* offset, const float* mask, int B, int C, int H, int W, int Co, int kh, int kw,
-                                int sh, int sw, int ph, int pw, int dh, int dw, int dg, float* output, int out_nhwc,
-                                int out_pix_pitch, int out_row_pitch, long long out_img_pitch, int act, float slope,
-                                int input_grouped);
-
-/*
- * The same forward with the implicit GEMM on the F16 matrix pipe, fp32 result (the arithmetic of C2M_CONV_SPLIT_F16X2: the
- * blended column value c = x0 + 2^-11 x1' in two round-to-nearest f16 pieces, per-tensor-scaled weights S w = wA + w1, three
- * products per k step, one fp32 accumulator, times 1/S): 3/32 of the fp32 pipe's matrix time, error of the class of the fp32
- * accumulation chain.  Geometries with >= 16 channels per (virtual) group, i.e. every DynAgg layer of the restoration network
- * (c2m_dcn_v2_relayout_f16x2_bytes == 0 otherwise).  Domain: |mask * bilinear sample| < 65520 -- beyond it outputs are not
- * finite and `range_flag` (device int, may be NULL; never cleared here) is set to 1: the caller recomputes with
- * c2m_dcn_v2_forward_nhwc_f32, as for the convolutions (c2m_conv3x3_desc.range_flag).
- */
+/* The weight image of C2M_DCN_F16X2; c2m_dcn_v2_relayout_f16x2_bytes == 0: the geometry has no such kernel (it needs >= 16
+ * channels per -- possibly virtual -- group; every DynAgg layer of the restoration network has them). */
 size_t c2m_dcn_v2_relayout_f16x2_bytes(int C, int Co, int kh, int kw, int dg);
 int c2m_dcn_v2_relayout_f16x2(c2m_stream_t stream, const float* weight, int C, int Co, int kh, int kw, int dg, void* wt);
-int c2m_dcn_v2_forward_nhwc_f16x2(c2m_stream_t stream, const float* input_bordered, const void* wt, const float* bias,
-                                  const float* offset, const float* mask, int B, int C, int H, int W, int Co, int kh, int kw,
-                                  int sh, int sw, int ph, int pw, int dh, int dw, int dg, float* output, int out_nhwc,
-                                  int out_pix_pitch, int out_row_pitch, long long out_img_pitch, int act, float slope,
-                                  int input_grouped, int* range_flag);
+
+enum { C2M_DCN_FP32 = 0, C2M_DCN_F16X2 = 1 };
+typedef struct c2m_dcn_nhwc_desc {
+  int B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, dg;   /* as c2m_dcn_v2_forward_f32 takes them */
+  const float* input_bordered;   /* the copy made by c2m_nchw_to_nhwc_bordered_f32 (or written by a convolution into such a buffer) */
+  int input_grouped;       /* 1 (C / dg == 8 only): input_bordered is group-major [B][dg][H+3][W+3][8] instead -- a 32-byte sample
+                              run then shares its 128-byte line with the neighbouring positions of the same group instead of with
+                              three other groups (c2m_conv3x3_desc.out2 writes this layout) */
+  const void* wt;          /* C2M_DCN_FP32: from c2m_dcn_v2_relayout_f32; C2M_DCN_F16X2: from c2m_dcn_v2_relayout_f16x2 */
+  const float* bias;       /* [Co] */
+  const float* offset;     /* planar, as c2m_dcn_v2_forward_f32 takes them */
+  const float* mask;
+  float* output;           /* out_nhwc = 0: planar [B][Co][Ho][Wo]; else channels-last with the pitches below (in floats) */
+  int out_nhwc, out_pix_pitch, out_row_pitch;
+  long long out_img_pitch;
+  int act;                 /* C2M_ACT_* (the lrelu that follows every DynAgg, ref_restoration_arch.py:152-154) */
+  float slope;             /* LeakyReLU negative slope */
+  int arith;               /* C2M_DCN_FP32 (0): implicit GEMM on the fp32 matrix pipe.  C2M_DCN_F16X2 (1): on the F16 matrix pipe,
+                              fp32 result (the arithmetic of C2M_CONV_SPLIT_F16X2: the blended column value c = x0 + 2^-11 x1' in
+                              two round-to-nearest f16 pieces, per-tensor-scaled weights S w = wA + w1, three products per k step,
+                              one fp32 accumulator, times 1/S): 3/32 of the fp32 pipe's matrix time, error of the class of the fp32
+                              accumulation chain.  Domain: |mask * bilinear sample| < 65520 -- beyond it outputs are not finite.
+                              Any other value gives C2M_ERR_INVALID_ARG */
+  int* range_flag;         /* C2M_DCN_F16X2 only, or NULL: device int set to 1 when an output left that domain (never cleared here);
+                              the caller recomputes with C2M_DCN_FP32, as for the convolutions (c2m_conv3x3_desc.range_flag) */
+} c2m_dcn_nhwc_desc;
+int c2m_dcn_v2_forward_nhwc(c2m_stream_t stream, const c2m_dcn_nhwc_desc* desc);
 
 size_t c2m_dcn_v2_backward_workspace_bytes(int B, int C, int H, int W, int Co, int kh, int kw, int sh, int sw, int ph,
                                            int pw, int dh, int dw, int dg);
@@ -306,7 +311,7 @@ typedef struct c2m_conv3x3_desc {
                               head run as 192 channels on 64-wide tiles + 24 on a 32-wide tile instead of 256 padded ones */
   float* out2;             /* NHWC + C2M_CONV_DIRECT only, or NULL: a second copy of the output in the 8-channel group-major
                               layout out2[b*img + (co/8)*plane + y*row + x*8 + co%8] (pitches in floats, multiples of 4) --
-                              what c2m_dcn_v2_forward_nhwc_f32(input_grouped = 1) gathers from.  Cout % 8 == 0 */
+                              what c2m_dcn_v2_forward_nhwc (input_grouped = 1) gathers from.  Cout % 8 == 0 */
   int out2_row_pitch;
   long long out2_plane_pitch, out2_img_pitch;
   int* range_flag;         /* C2M_CONV_SPLIT_F16X2 only, or NULL: device int the kernel sets to 1 when an input activation lies
@@ -321,6 +326,13 @@ typedef struct c2m_conv3x3_desc {
                               the tile goes HBM -> LDS by DMA without passing registers); bit 1: `out` holds bf16; bit 2 / 3:
                               res1 / res2 hold bf16.  Pointers are passed as float* regardless.  Accumulation, bias,
                               activation and the residual adds stay fp32; one rounding at the store */
+  int roi_tiles_y, roi_tiles_x;   /* both 0: the whole tile grid.  Both > 0 (at most the grid of the full launch, else
+                              C2M_ERR_INVALID_ARG; tile shape: c2m_conv3x3_roi_tile): the top-left roi_tiles_y x roi_tiles_x pixel
+                              tiles only.  H, W, the sources and the outputs stay those of the full launch: halos are read from
+                              the full-size input, the tiles computed come out bit for bit as the full launch writes them,
+                              everything else is left untouched (C2M_OUT_NHWC_MAXPOOL2: the pooled pixels of those tiles).  Split
+                              algorithms only, else C2M_ERR_UNSUPPORTED.  Anything else (one of them 0, a negative value) gives
+                              C2M_ERR_INVALID_ARG */
 } c2m_conv3x3_desc;
 #define C2M_IO_SRC_BF16 1
 #define C2M_IO_OUT_BF16 2
@@ -349,11 +361,6 @@ int c2m_conv3x3_relayout_split_f32(c2m_stream_t stream, const float* weight, int
  * pieces = 2 (then one more launch reduces max |w| of those tensors for their scales). */
 int c2m_conv3x3_relayout_split_multi(c2m_stream_t stream, const long long* jobs, int njobs, long long nblocks, int any_f16);
 int c2m_conv3x3_nhwc_f32(c2m_stream_t stream, const c2m_conv3x3_desc* desc);
-/* The same launch on the top-left roi_tiles_y x roi_tiles_x pixel tiles only (both > 0, at most the grid of the full launch;
- * tile shape: c2m_conv3x3_roi_tile).  H, W, the sources and the outputs are those of the full launch: halos are read from the
- * full-size input, the tiles computed come out bit for bit as c2m_conv3x3_nhwc_f32 writes them, everything else is left
- * untouched (C2M_OUT_NHWC_POOL2: the pooled pixels of those tiles).  Split algorithms only, else C2M_ERR_UNSUPPORTED. */
-int c2m_conv3x3_nhwc_roi_f32(c2m_stream_t stream, const c2m_conv3x3_desc* desc, int roi_tiles_y, int roi_tiles_x);
 /* Pixel tile of a workgroup: of c2m_conv3x3_rgb64_f32 (rgb64 != 0) or of the split algorithms of c2m_conv3x3_nhwc_f32. */
 int c2m_conv3x3_roi_tile(int rgb64, int* tile_h, int* tile_w);
 
@@ -376,21 +383,28 @@ int c2m_conv3x3_wgrad_f32(c2m_stream_t stream, const c2m_conv_src* src, int nsrc
 
 /*
  * First layer of an image tower -- 3 input channels, 64 output channels (vgg conv1_1, vgg_arch.py:107-123; conv_first,
- * ref_restoration_arch.py:30): image [B][3][H][W] planar fp32, weight [64][3][3][3], bias [64] or NULL;
- * mean / std [3] (both or neither): (image - mean[c]) / std[c] is applied first (vgg_arch.py:137-138), zero padding in the
- * normalised domain.  Output channels-last with the given pitches (floats) + optional activation; out2: optional
- * 8-channel group-major twin (see c2m_conv3x3_desc.out2).  One image (12 H W bytes) and eight output rows are addressed with
- * 32-bit byte offsets; C2M_ERR_UNSUPPORTED beyond 2^31 (an image of 13 000 x 13 000 pixels, rows of 10^6 pixels).
+ * ref_restoration_arch.py:30).  (image - mean[c]) / std[c] is applied first (vgg_arch.py:137-138), zero padding in the
+ * normalised domain.  One image (12 H W bytes) and eight output rows are addressed with 32-bit byte offsets;
+ * C2M_ERR_UNSUPPORTED beyond 2^31 (an image of 13 000 x 13 000 pixels, rows of 10^6 pixels).
  */
-int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                          const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
-                          int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2, int out2_row_pitch,
-                          long long out2_plane_pitch, long long out2_img_pitch);
-/* ... on the top-left roi_tiles_y x roi_tiles_x tiles only (see c2m_conv3x3_nhwc_roi_f32). */
-int c2m_conv3x3_rgb64_roi_f32(c2m_stream_t stream, const float* image, int B, int H, int W, const float* weight,
-                              const float* bias, const float* mean, const float* std_, int act, float slope, float* out,
-                              int out_pix_pitch, int out_row_pitch, long long out_img_pitch, float* out2, int out2_row_pitch,
-                              long long out2_plane_pitch, long long out2_img_pitch, int roi_tiles_y, int roi_tiles_x);
+typedef struct c2m_conv3x3_rgb64_desc {
+  const float* image;      /* [B][3][H][W] planar fp32 */
+  int B, H, W;
+  const float* weight;     /* [64][3][3][3] */
+  const float* bias;       /* [64] or NULL */
+  const float* mean;       /* [3]; mean and std_: both or neither */
+  const float* std_;
+  int act;                 /* C2M_ACT_* */
+  float slope;
+  float* out;              /* channels-last with the pitches below (in floats) */
+  int out_pix_pitch, out_row_pitch;
+  long long out_img_pitch;
+  float* out2;             /* optional 8-channel group-major twin (see c2m_conv3x3_desc.out2), or NULL */
+  int out2_row_pitch;
+  long long out2_plane_pitch, out2_img_pitch;
+  int roi_tiles_y, roi_tiles_x;   /* as c2m_conv3x3_desc.roi_tiles_y / roi_tiles_x (tile shape: c2m_conv3x3_roi_tile(1)) */
+} c2m_conv3x3_rgb64_desc;
+int c2m_conv3x3_rgb64_f32(c2m_stream_t stream, const c2m_conv3x3_rgb64_desc* desc);
 
 /*
  * The padding band of a zero-padded Ref image (csrc/ref_band.hip).

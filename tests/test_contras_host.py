@@ -32,7 +32,7 @@ def test_header_declares_and_library_exports_the_loss_entry_points():
     lib = ctypes.CDLL(c2m_amd.LIB_PATH)
     for name in SYMBOLS:
         assert hasattr(lib, name), name
-    assert lib.c2m_abi_version() == 5
+    assert lib.c2m_abi_version() == 6
 
 
 def test_workspace_query_and_argument_checks():

@@ -1,5 +1,5 @@
 """GPU: the Ref padding-band path -- convolutions launched on the live tiles only + band fill from a template -- returns the
-bits of the full launch (c2m_amd.ops.vgg_stack_forward(live=...), csrc/ref_band.hip, the *_roi_f32 entry points).
+bits of the full launch (c2m_amd.ops.vgg_stack_forward(live=...), csrc/ref_band.hip, roi_tiles_y / roi_tiles_x of the convolution descriptors).
 
 Every comparison is torch.equal.  Canvases are the smallest with real tile structure at all three scales (128 x 160 and
 160 x 128: H % 32 == 0 for the two pools and the 8-row tiles; the coarsest scale is then 32 x 40 / 40 x 32 pixels, one full

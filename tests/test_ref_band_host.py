@@ -115,12 +115,38 @@ def test_header_and_library_agree_on_the_new_entry_points():
     hdr = open(os.path.join(REPO, "include", "c2m_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = ctypes.CDLL(c2m_amd.LIB_PATH)
-    for name in ("c2m_conv3x3_nhwc_roi_f32", "c2m_conv3x3_rgb64_roi_f32", "c2m_conv3x3_roi_tile", "c2m_ref_live_extent_f32",
-                 "c2m_band_fill_f32"):
+    for name in ("c2m_conv3x3_roi_tile", "c2m_ref_live_extent_f32", "c2m_band_fill_f32"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert hasattr(lib, name), name
-    assert lib.c2m_abi_version() == 5
+    # ABI 6: the ROI is two fields of the convolution descriptors, the fused DCNv2 forward one entry point with a descriptor
+    for name in ("c2m_conv3x3_nhwc_roi_f32", "c2m_conv3x3_rgb64_roi_f32", "c2m_dcn_v2_forward_nhwc_f32", "c2m_dcn_v2_forward_nhwc_f16x2"):
+        assert not re.search(r"\b%s\b" % name, hdr), name
+        assert not hasattr(lib, name), name
+    assert lib.c2m_abi_version() == 6
     # the fill refuses geometries whose clamp zones would overlap, before anything is launched (no GPU needed)
     L = c2m_amd._lib.lib()
     assert L.c2m_band_fill_f32(None, 16, 1, 4, 4, 40, 4, 4, 160, 0, 640, 16, 12, 20, 4, 80, 0, 4, 32, 3, 3, 0) != 0
     assert L.c2m_conv3x3_roi_tile(0, None, None) != 0
+    # the ROI rule of both descriptors, checked before any launch: fake (non-null, 16-byte aligned) pointers are never read
+    INVALID_ARG, UNSUPPORTED, fake = 1, 2, 0x1000
+    _lib = c2m_amd._lib
+    assert {"roi_tiles_y", "roi_tiles_x"} <= {n for n, _ in _lib.Conv3x3Desc._fields_}
+    d = _lib.Conv3x3Desc(B=1, H=16, W=64, Cin=32, Cout=32, nsrc=1, wr=fake, out=fake, out_pix_pitch=32, out_row_pitch=32 * 64,
+                         out_img_pitch=32 * 64 * 16, algo=5)
+    d.src[0] = _lib.ConvSrc(ptr=fake, C=32, pix_pitch=32, row_pitch=32 * 64, img_pitch=32 * 64 * 16)
+    r = _lib.Conv3x3Rgb64Desc(image=fake, B=1, H=16, W=64, weight=fake, out=fake, out_pix_pitch=64, out_row_pitch=64 * 64,
+                              out_img_pitch=64 * 64 * 16)
+    for roi in ((1, 0), (0, 1), (-1, 1), (1, -1), (-1, -1)):
+        d.roi_tiles_y, d.roi_tiles_x = r.roi_tiles_y, r.roi_tiles_x = roi
+        assert L.c2m_conv3x3_nhwc_f32(None, d) == INVALID_ARG, roi
+        assert L.c2m_conv3x3_rgb64_f32(None, r) == INVALID_ARG, roi
+    d.roi_tiles_y, d.roi_tiles_x = r.roi_tiles_y, r.roi_tiles_x = 100, 1     # larger than the full grid
+    assert L.c2m_conv3x3_nhwc_f32(None, d) == INVALID_ARG and L.c2m_conv3x3_rgb64_f32(None, r) == INVALID_ARG
+    d.roi_tiles_y, d.roi_tiles_x, d.algo = 1, 1, 0                            # C2M_CONV_DIRECT has no ROI launch
+    assert L.c2m_conv3x3_nhwc_f32(None, d) == UNSUPPORTED
+    assert L.c2m_conv3x3_nhwc_f32(None, None) == INVALID_ARG and L.c2m_conv3x3_rgb64_f32(None, None) == INVALID_ARG
+    # the fused DCNv2 forward: no descriptor, and an arithmetic it does not have
+    assert L.c2m_dcn_v2_forward_nhwc(None, None) == INVALID_ARG
+    g = _lib.DcnNhwcDesc(B=1, C=64, H=8, W=8, Co=64, kh=3, kw=3, sh=1, sw=1, ph=1, pw=1, dh=1, dw=1, dg=8, input_bordered=fake,
+                         wt=fake, bias=fake, offset=fake, mask=fake, output=fake, arith=2)
+    assert L.c2m_dcn_v2_forward_nhwc(None, g) == INVALID_ARG

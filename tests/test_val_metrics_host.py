@@ -14,7 +14,7 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_header_declares_and_library_exports_the_new_symbols_at_abi_5():
+def test_header_declares_and_library_exports_the_new_symbols_at_abi_6():
     import c2m_amd
     hdr = open(os.path.join(REPO, "include", "c2m_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
@@ -22,7 +22,7 @@ def test_header_declares_and_library_exports_the_new_symbols_at_abi_5():
     lib = ctypes.CDLL(c2m_amd.LIB_PATH)
     for name in ("c2m_val_metrics_workspace_bytes", "c2m_val_metrics_f32"):
         assert name in declared and hasattr(lib, name), name
-    assert lib.c2m_abi_version() == 5 and c2m_amd._lib.ABI_VERSION == 5
+    assert lib.c2m_abi_version() == 6 and c2m_amd._lib.ABI_VERSION == 6
     # pure size arithmetic, no device: [B][tiles][3] float64, and 0 for a cropped window below 11 pixels
     L = c2m_amd.lib()
     th, tw = c2m_amd.ops.val_metrics_tile()
