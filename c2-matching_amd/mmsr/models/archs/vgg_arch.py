@@ -142,6 +142,10 @@ class VGGFeatureExtractor(nn.Module):
                 std=self.std if self.use_input_norm else None, grouped8_taps=getattr(self, 'grouped8_taps', ()),
                 fast=getattr(self, 'fast_conv', False),
                 live=_ops.ref_live_extent_shared(x) if getattr(self, 'ref_band', False) else None), x.device)
+        return self.forward_stock(x)
+
+    def forward_stock(self, x):
+        """The stack layer by layer on torch's own operators (what autograd differentiates; any device and dtype)."""
         if self.use_input_norm:
             x = (x - self.mean) / self.std
         taps = {}

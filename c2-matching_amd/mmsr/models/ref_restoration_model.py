@@ -1,8 +1,12 @@
-"""Stage-3 (MSE yaml) slice of the reference's ``RefRestorationModel`` (ref_restoration_model.py:21-43, 47-87,
-186-279): net construction through the registry, the four Adam parameter groups, ``feed_data`` / ``optimize_parameters``
-with the pixel loss / ``test``.  GAN, perceptual, texture losses and LR schedulers are outside the
-hot path and are not provided here -- ``mmsr/train.py`` of the reference keeps using its own
-model file; this class is what bench/tests drive.
+"""Stage-3 slice of the reference's ``RefRestorationModel`` (ref_restoration_model.py:21-43, 47-87, 186-279): net
+construction through the registry, the four Adam parameter groups, ``feed_data`` / ``optimize_parameters`` / ``test``.  The
+losses: the pixel loss (the MSE yaml) and, where ``train.perceptual_opt`` is present, the perceptual loss of the GAN yaml
+(mmsr/models/losses.py) with the reference's two phases (ref_restoration_model.py:199-269 with ``net_d = None``): up to
+``train.net_g_pretrain_steps`` the pixel loss alone (log key ``l_pix``), afterwards pixel + perceptual (``l_g_pix``,
+``l_g_percep``).  The loss module sits bare on the device: it has no trainable parameter, is never DDP-wrapped and never
+enters a checkpoint.  Without ``perceptual_opt`` the step, its log key and the graph handling are what they were.  The
+discriminator (``network_d`` / ``gan_type``), ``style_opt``, ``texture_opt`` and the LR schedulers are not provided here --
+``mmsr/train.py`` of the reference keeps using its own model file; this class is what bench/tests drive.
 
 Validation: ``nondist_validation`` computes PSNR / PSNR_Y / SSIM_Y with the reference's rules
 (ref_restoration_model.py:295-370) but on the device: one kernel reads SR and GT once and leaves three sums per image and,
@@ -15,7 +19,9 @@ correspondence + net_g forward + L1 + backward + Adam) is a launch-bound chain o
 stage-3 crop size (GT 160x160, batch 4 per GPU): the host spends more time launching than the GPU computing.  The step is
 captured once into a hipGraph (torch.cuda.CUDAGraph: static input buffers filled by ``feed_data``, Adam in capturable
 mode, two eager warm-up steps so that allocator, MIOpen find and lazy initialisation stay outside the capture) and
-replayed per ``optimize_parameters`` call -- same arithmetic, same kernels, one launch.
+replayed per ``optimize_parameters`` call -- same arithmetic, same kernels, one launch.  With a perceptual loss each of the
+two phases is its own captured step: crossing ``net_g_pretrain_steps`` drops the graph, and the next calls warm up and capture
+again, as after a new input geometry.
 """
 import collections
 import copy
@@ -67,6 +73,13 @@ class RefRestorationModel(BaseModel):
             self._build_optimizer()
             self.cri_pix = torch.nn.L1Loss()  # pixel_criterion: L1Loss, pixel_weight 1.0 (stage3_restoration_mse.yml:84-85)
             self.pixel_weight = float(self.opt['train'].get('pixel_weight', 1.0))
+            # the GAN yaml's perceptual_opt (ref_restoration_model.py:119-125, :165); absent: the pixel-loss step as it was
+            self.cri_perceptual = None
+            self.net_g_pretrain_steps = int(self.opt['train'].get('net_g_pretrain_steps') or 0)
+            self._pretrain = False    # the phase of the step being run / captured
+            if self.opt['train'].get('perceptual_opt'):
+                from mmsr.models.losses import PerceptualLoss
+                self.cri_perceptual = PerceptualLoss(**self.opt['train']['perceptual_opt']).to(self.device)
 
     def _build_optimizer(self):
         """Adam with the reference's four groups keyed on parameter names (ref_restoration_model.py:47-87)."""
@@ -115,6 +128,12 @@ class RefRestorationModel(BaseModel):
             self.pre_offset, self.img_ref_feat = self.net_map(self.features, self.img_ref)
 
     def optimize_parameters(self, step):
+        if self.cri_perceptual is not None:
+            pretrain = step <= self.net_g_pretrain_steps
+            if pretrain != self._pretrain:
+                self._pretrain = pretrain
+                self._graph, self._graph_calls = None, 0    # the other phase is another step: warm up and capture again
+                self.log_dict.clear()
         if self._graph_on:
             return self._optimize_graphed()
         self._train_step()
@@ -124,9 +143,26 @@ class RefRestorationModel(BaseModel):
         self.output = self.net_g(self.img_in_lq, self.pre_offset, self.img_ref_feat)
         self.optimizer_g.zero_grad()
         l_pix = self.cri_pix(self.output, self.gt) * self.pixel_weight
+        if self.cri_perceptual is not None:
+            return self._perceptual_step(l_pix)
         l_pix.backward()  # DCNv2 backward x3; DDP all-reduces net_g's gradients (RCCL) while it runs
         self.optimizer_g.step()
         self.log_dict['l_g_pix'] = l_pix.detach()  # no .item(): the reference's per-step host sync is dropped
+
+    def _perceptual_step(self, l_pix):
+        """The rest of a step of the GAN yaml without a discriminator (ref_restoration_model.py:199-207, :240-269); the log
+        values stay device tensors and nothing is read back."""
+        if self._pretrain:
+            l_pix.backward()
+            self.optimizer_g.step()
+            self.log_dict['l_pix'] = l_pix.detach()
+            return
+        l_g_percep, _ = self.cri_perceptual(self.output, self.gt)   # (None with perceptual_weight 0, as in the reference)
+        (l_pix if l_g_percep is None else l_pix + l_g_percep).backward()
+        self.optimizer_g.step()
+        self.log_dict['l_g_pix'] = l_pix.detach()
+        if l_g_percep is not None:
+            self.log_dict['l_g_percep'] = l_g_percep.detach()
 
     GRAPH_WARMUP_STEPS = 2
 
