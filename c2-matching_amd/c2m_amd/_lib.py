@@ -1,4 +1,4 @@
-"""ctypes loader for libc2m_hip.so (the C-ABI of include/c2m_hip.h).
+"""ctypes loader for libc2m_hip.so (the C-ABI of include/c2m_hip.h and, for the GAN additions, include/c2m_gan_hip.h).
 
 There is NO fallback: if the shared library is missing, was built for another ABI version, or a call returns a
 non-zero status, this module raises.  torch must be imported first so that the library binds to the HIP runtime
@@ -139,6 +139,11 @@ def _declare(L):
     L.c2m_val_metrics_workspace_bytes.restype = _sz
     L.c2m_val_metrics_workspace_bytes.argtypes = [_i] * 4
     L.c2m_val_metrics_f32.argtypes = [_vp, ctypes.POINTER(ImageSrc), ctypes.POINTER(ImageSrc)] + [_i] * 7 + [_vp] * 4 + [_sz]
+    # include/c2m_gan_hip.h (additive: same library, same ABI version)
+    L.c2m_gp_penalty_workspace_bytes.restype = _sz
+    L.c2m_gp_penalty_workspace_bytes.argtypes = [_i, _ll]
+    L.c2m_gp_penalty_forward_f32.argtypes = [_vp, _vp, _i, _ll, _vp, _vp, _vp, _sz]
+    L.c2m_gp_penalty_backward_f32.argtypes = [_vp, _vp, _vp, _vp, _i, _ll, _vp]
 
 
 def lib():

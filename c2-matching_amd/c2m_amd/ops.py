@@ -2104,3 +2104,52 @@ def val_metrics(sr, gt, crop_border=4, valid_hw=None, images=None):
     if images:
         out['sr_u8'], out['gt_u8'] = s8, g8
     return out
+
+
+# ---- the WGAN-GP penalty on the critic's input gradient (csrc/gp_penalty.hip, include/c2m_gan_hip.h) -----------------------
+
+class _GradientPenaltyFn(torch.autograd.Function):
+    """G fp32 [N, ...] -> (mean_n (||G[n]||_2 - 1)^2 as a 0-d tensor, norms [N]).  G is the output of
+    autograd.grad(create_graph=True), so the gradient this returns for it feeds the critic's double-backward graph; the
+    backward itself is not differentiable again.  norms is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, G):
+        N, M = G.shape[0], G.numel() // G.shape[0]
+        L = _lib.lib()
+        nbytes = int(L.c2m_gp_penalty_workspace_bytes(N, M))
+        if nbytes == 0:
+            raise _lib.C2MError(f"c2m_gp_penalty_workspace_bytes: unsupported shape {tuple(G.shape)}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+        norms = torch.empty(N, dtype=torch.float32, device=G.device)
+        out = torch.empty((), dtype=torch.float32, device=G.device)
+        with torch.cuda.device(G.device):
+            _lib.check(L.c2m_gp_penalty_forward_f32(_stream(), G.data_ptr(), N, M, norms.data_ptr(), out.data_ptr(),
+                                                    ws.data_ptr(), nbytes), "c2m_gp_penalty_forward_f32")
+        ctx.save_for_backward(G, norms)
+        ctx.mark_non_differentiable(norms)
+        return out, norms
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, _g_norms):
+        G, norms = ctx.saved_tensors
+        N, M = G.shape[0], G.numel() // G.shape[0]
+        gout = gout.to(torch.float32).contiguous()       # stays on the device: the kernel reads it there
+        dG = torch.empty_like(G)
+        with torch.cuda.device(G.device):
+            _lib.check(_lib.lib().c2m_gp_penalty_backward_f32(_stream(), G.data_ptr(), norms.data_ptr(), gout.data_ptr(), N, M,
+                                                              dG.data_ptr()), "c2m_gp_penalty_backward_f32")
+        return dG
+
+
+def gradient_penalty(grad, with_norms=False):
+    """The WGAN-GP penalty ``((grad.flatten(1).norm(2, dim=1) - 1) ** 2).mean()`` of fp32 ``grad`` [N, ...] on the GPU, in two
+    launches forward and one backward (no atomics: the same input gives the same bits on every call).  Differentiable once
+    with respect to ``grad``; a sample whose gradient is all zero gets a zero gradient, as torch's norm gives it.
+    -> the 0-d penalty, or (penalty, norms [N]) with with_norms."""
+    g = _dev_f32(grad, "grad")
+    if g.dim() < 2 or g.numel() == 0:
+        raise _lib.C2MError(f"grad must be a non-empty [N, ...] tensor with at least two dimensions, got {tuple(g.shape)}")
+    out, norms = _GradientPenaltyFn.apply(g)
+    return (out, norms) if with_norms else out

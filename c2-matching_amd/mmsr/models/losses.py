@@ -1,6 +1,9 @@
-"""The perceptual (VGG feature) loss of stage-3 GAN training: ``PerceptualLoss`` with the semantics of the reference's class
-of that name (losses.py:141-238; options/train/stage3_restoration_gan.yml: ``relu5_1`` of VGG19, ``criterion: fro``, weight
-1e-4), written for this project.
+"""The losses of stage-3 GAN training, written for this project with the semantics of the reference's classes of the same
+names: ``PerceptualLoss`` (losses.py:141-238; options/train/stage3_restoration_gan.yml: ``relu5_1`` of VGG19, ``criterion:
+fro``, weight 1e-4), ``GANLoss`` (losses.py:275-363; ``gan_type: wgan``) and ``GradientPenaltyLoss`` (losses.py:366-428;
+``grad_penalty_weight 10``), the last two at the end of this file.
+
+``PerceptualLoss``:
 
 Two deviations, both deliberate:
 * ``criterion='l2'`` builds ``torch.nn.MSELoss()``.  The reference names ``torch.nn.L2loss``, which does not exist, and raises
@@ -15,6 +18,7 @@ path for the frozen tower was built and measured, and is not shipped: DESIGN.md 
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from mmsr.models.archs.vgg_arch import VGGFeatureExtractor
 
@@ -81,3 +85,68 @@ class PerceptualLoss(nn.Module):
                 style = style + self.criterion(self._gram(fx[k]), self._gram(fg[k])) * self.layer_weights[k]
             style = style * self.style_weight
         return percep, style
+
+
+class GANLoss(nn.Module):
+    """forward(input, target_is_real, is_disc=False) -> the adversarial loss of a critic prediction.
+
+    gan_type 'vanilla': binary cross-entropy with logits against the label value; 'lsgan': mean squared error against the
+    label value; 'wgan': -mean(input) for a real target, +mean(input) for a fake one; 'hinge': mean(relu(1 -/+ input)) for the
+    critic, -mean(input) for the generator.  loss_weight scales the generator's loss only (is_disc False); the critic's own
+    loss always has weight 1."""
+
+    def __init__(self, gan_type, real_label_val=1.0, fake_label_val=0.0, loss_weight=1.0):
+        super().__init__()
+        if gan_type not in ('vanilla', 'lsgan', 'wgan', 'hinge'):
+            raise NotImplementedError(f'GAN type {gan_type} is not implemented.')
+        self.gan_type = gan_type
+        self.real_label_val = real_label_val
+        self.fake_label_val = fake_label_val
+        self.loss_weight = loss_weight
+
+    def forward(self, input, target_is_real, is_disc=False):
+        if self.gan_type == 'wgan':
+            loss = -input.mean() if target_is_real else input.mean()
+        elif self.gan_type == 'hinge':
+            if is_disc:
+                loss = F.relu(1 - input if target_is_real else 1 + input).mean()
+            else:
+                loss = -input.mean()
+        else:
+            label = torch.full_like(input, self.real_label_val if target_is_real else self.fake_label_val)
+            loss = F.binary_cross_entropy_with_logits(input, label) if self.gan_type == 'vanilla' else F.mse_loss(input, label)
+        return loss if is_disc else loss * self.loss_weight
+
+
+class GradientPenaltyLoss(nn.Module):
+    """The WGAN-GP penalty: forward(discriminator, real_data, fake_data, alpha=None) ->
+    loss_weight * mean_n (||d D(x^)/d x^ [n]||_2 - 1)^2 at x^ = alpha * real + (1 - alpha) * fake.detach().
+
+    alpha: [N,1,1,1]; None draws it uniformly in [0, 1) from torch's generator ON the inputs' device (the reference draws on the
+    host and copies: a host-to-device copy in every step); a given alpha is used as it is.  No gradient reaches fake_data: the
+    reference wraps x^ in ``autograd.Variable(..., requires_grad=True)``, which on current torch makes it a leaf.  The
+    reference's inpainting mask is not provided.
+
+    fused (default True): an fp32 gradient on the GPU goes through ``c2m_amd.ops.gradient_penalty`` (two launches forward, one
+    backward); anything else -- CPU tensors, other dtypes, fused=False -- takes the torch composition of the same expression."""
+
+    def __init__(self, loss_weight=1.0, fused=True):
+        super().__init__()
+        self.loss_weight = loss_weight
+        self.fused = fused
+
+    @staticmethod
+    def penalty_composition(gradients):
+        return ((gradients.flatten(1).norm(2, dim=1) - 1) ** 2).mean()
+
+    def forward(self, discriminator, real_data, fake_data, alpha=None):
+        if alpha is None:
+            alpha = torch.rand(real_data.size(0), 1, 1, 1, dtype=real_data.dtype, device=real_data.device)
+        interpolates = (alpha * real_data + (1. - alpha) * fake_data.detach()).detach().requires_grad_(True)
+        gradients = torch.autograd.grad(discriminator(interpolates).sum(), interpolates, create_graph=True)[0]
+        if self.fused and gradients.is_cuda and gradients.dtype == torch.float32:
+            from c2m_amd import ops
+            penalty = ops.gradient_penalty(gradients)
+        else:
+            penalty = self.penalty_composition(gradients)
+        return penalty * self.loss_weight

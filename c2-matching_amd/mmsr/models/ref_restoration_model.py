@@ -1,12 +1,22 @@
 """Stage-3 slice of the reference's ``RefRestorationModel`` (ref_restoration_model.py:21-43, 47-87, 186-279): net
 construction through the registry, the four Adam parameter groups, ``feed_data`` / ``optimize_parameters`` / ``test``.  The
 losses: the pixel loss (the MSE yaml) and, where ``train.perceptual_opt`` is present, the perceptual loss of the GAN yaml
-(mmsr/models/losses.py) with the reference's two phases (ref_restoration_model.py:199-269 with ``net_d = None``): up to
+(mmsr/models/losses.py) with the reference's two phases (ref_restoration_model.py:199-269): up to
 ``train.net_g_pretrain_steps`` the pixel loss alone (log key ``l_pix``), afterwards pixel + perceptual (``l_g_pix``,
 ``l_g_percep``).  The loss module sits bare on the device: it has no trainable parameter, is never DDP-wrapped and never
-enters a checkpoint.  Without ``perceptual_opt`` the step, its log key and the graph handling are what they were.  The
-discriminator (``network_d`` / ``gan_type``), ``style_opt``, ``texture_opt`` and the LR schedulers are not provided here --
-``mmsr/train.py`` of the reference keeps using its own model file; this class is what bench/tests drive.
+enters a checkpoint.  Without ``perceptual_opt`` and ``network_d`` the step, its log key and the graph handling are what they
+were.  ``style_opt``, ``texture_opt`` and the LR schedulers are not provided here -- ``mmsr/train.py`` of the reference keeps
+using its own model file; this class is what bench/tests drive.
+
+The critic (``network_d`` together with ``train.gan_type``; single process): ``net_d`` through the registry, its own Adam
+(``lr_d``, ``weight_decay_d``, ``beta_d``) as the second entry of ``self.optimizers``, ``GANLoss`` and, with
+``grad_penalty_weight > 0``, ``GradientPenaltyLoss``.  After the pretrain phase every step first trains the critic on
+``D(gt)``, ``D(output.detach())`` and the penalty, then -- when ``(step - pretrain) % net_d_steps == 0`` and
+``(step - pretrain) > net_d_init_steps`` -- the generator on pixel + perceptual + ``cri_gan(D(output), True)`` with the
+critic's parameters frozen (ref_restoration_model.py:209-269).  Log keys in the reference's order: ``l_d_real``,
+``out_d_real``, ``l_d_fake``, ``out_d_fake``, ``l_grad_penalty``, ``l_g_pix``, ``l_g_percep``, ``l_g_gan``, all device tensors.
+The critic's BatchNorm layers run in train mode in each of its three or four forwards of a step, as in the reference.
+``opt['dist']`` with a critic raises NotImplementedError.
 
 Validation: ``nondist_validation`` computes PSNR / PSNR_Y / SSIM_Y with the reference's rules
 (ref_restoration_model.py:295-370) but on the device: one kernel reads SR and GT once and leaves three sums per image and,
@@ -21,7 +31,8 @@ captured once into a hipGraph (torch.cuda.CUDAGraph: static input buffers filled
 mode, two eager warm-up steps so that allocator, MIOpen find and lazy initialisation stay outside the capture) and
 replayed per ``optimize_parameters`` call -- same arithmetic, same kernels, one launch.  With a perceptual loss each of the
 two phases is its own captured step: crossing ``net_g_pretrain_steps`` drops the graph, and the next calls warm up and capture
-again, as after a new input geometry.
+again, as after a new input geometry.  With a critic only the pretrain phase is captured: the GAN phase
+(``autograd.grad(create_graph=True)``, a second optimizer) runs eagerly.
 """
 import collections
 import copy
@@ -45,6 +56,11 @@ class RefRestorationModel(BaseModel):
 
     def __init__(self, opt):
         super().__init__(opt)
+        with_critic = bool(self.is_train and opt.get('network_d') and (opt.get('train') or {}).get('gan_type'))
+        if with_critic and opt.get('dist'):
+            raise NotImplementedError("network_d with opt['dist']: the critic's three forwards before one backward and the "
+                                      "penalty's autograd.grad are not wired for DistributedDataParallel; train the GAN "
+                                      "phase in a single process")
         opt = copy.deepcopy(opt)  # the factories pop 'type'
         self.net_g = self.model_to_device(networks.define_net_g(opt))
         # net_map has no trainable parameters; net_extractor's never receive gradients in stage 3: both stay bare
@@ -80,6 +96,11 @@ class RefRestorationModel(BaseModel):
             if self.opt['train'].get('perceptual_opt'):
                 from mmsr.models.losses import PerceptualLoss
                 self.cri_perceptual = PerceptualLoss(**self.opt['train']['perceptual_opt']).to(self.device)
+            # the GAN yaml's network_d / gan_type block (ref_restoration_model.py:92-107, :143-179); absent: nothing changes
+            self.net_d = self.cri_gan = self.cri_grad_penalty = None
+            if with_critic:
+                self._build_critic(opt, path)
+            self._phased = self.cri_perceptual is not None or self.net_d is not None
 
     def _build_optimizer(self):
         """Adam with the reference's four groups keyed on parameter names (ref_restoration_model.py:47-87)."""
@@ -101,6 +122,24 @@ class RefRestorationModel(BaseModel):
             lr=t['lr_g'], weight_decay=t.get('weight_decay_g', 0), betas=tuple(t['beta_g']),
             capturable=self._graph_on)   # (step counters on the device: required inside a captured step)
         self.optimizers.append(self.optimizer_g)
+
+    def _build_critic(self, opt, path):
+        from mmsr.models.losses import GANLoss, GradientPenaltyLoss
+        t = self.opt['train']
+        self.net_d = self.model_to_device(networks.define_net_d(opt))
+        if path.get('pretrain_model_d'):
+            self.load_network(self.net_d, path['pretrain_model_d'], path.get('strict_load', True))
+        self.net_d.train()
+        self.cri_gan = GANLoss(t['gan_type'], real_label_val=1.0, fake_label_val=0.0, loss_weight=t['gan_weight']).to(self.device)
+        if (t.get('grad_penalty_weight') or 0) > 0:
+            self.cri_grad_penalty = GradientPenaltyLoss(loss_weight=t['grad_penalty_weight']).to(self.device)
+        self.net_d_steps = int(t.get('net_d_steps') or 1)
+        self.net_d_init_steps = int(t.get('net_d_init_steps') or 0)
+        self._step = 0
+        self._gan_eager_logged = False
+        self.optimizer_d = torch.optim.Adam(self.net_d.parameters(), lr=t['lr_d'], weight_decay=t.get('weight_decay_d', 0),
+                                            betas=tuple(t['beta_d']))
+        self.optimizers.append(self.optimizer_d)   # save_training_state / resume_training carry it
 
     _FEED = (('img_in_lq', 'img_in_lq'), ('img_ref', 'img_ref'), ('gt', 'img_in'), ('match_img_in', 'img_in_up'))
 
@@ -128,12 +167,21 @@ class RefRestorationModel(BaseModel):
             self.pre_offset, self.img_ref_feat = self.net_map(self.features, self.img_ref)
 
     def optimize_parameters(self, step):
-        if self.cri_perceptual is not None:
+        if self._phased:
             pretrain = step <= self.net_g_pretrain_steps
             if pretrain != self._pretrain:
                 self._pretrain = pretrain
                 self._graph, self._graph_calls = None, 0    # the other phase is another step: warm up and capture again
                 self.log_dict.clear()
+        if self.net_d is not None:
+            self._step = step
+            if self._graph_on and not self._pretrain:
+                # autograd.grad(create_graph=True) and a second optimizer inside a capture are untried: the GAN phase is eager
+                if not self._gan_eager_logged:
+                    logger.info('hip_graph: the GAN phase (critic + gradient penalty) runs eagerly; only the pretrain phase '
+                                'is captured.')
+                    self._gan_eager_logged = True
+                return self._train_step()
         if self._graph_on:
             return self._optimize_graphed()
         self._train_step()
@@ -143,26 +191,77 @@ class RefRestorationModel(BaseModel):
         self.output = self.net_g(self.img_in_lq, self.pre_offset, self.img_ref_feat)
         self.optimizer_g.zero_grad()
         l_pix = self.cri_pix(self.output, self.gt) * self.pixel_weight
-        if self.cri_perceptual is not None:
+        if self._phased:
             return self._perceptual_step(l_pix)
         l_pix.backward()  # DCNv2 backward x3; DDP all-reduces net_g's gradients (RCCL) while it runs
         self.optimizer_g.step()
         self.log_dict['l_g_pix'] = l_pix.detach()  # no .item(): the reference's per-step host sync is dropped
 
     def _perceptual_step(self, l_pix):
-        """The rest of a step of the GAN yaml without a discriminator (ref_restoration_model.py:199-207, :240-269); the log
-        values stay device tensors and nothing is read back."""
+        """The rest of a step of the GAN yaml (ref_restoration_model.py:199-269): the pretrain step, or the critic's step (with a
+        critic) followed by the generator's where the step gating allows it; the log values stay device tensors and nothing is
+        read back."""
         if self._pretrain:
             l_pix.backward()
             self.optimizer_g.step()
             self.log_dict['l_pix'] = l_pix.detach()
             return
-        l_g_percep, _ = self.cri_perceptual(self.output, self.gt)   # (None with perceptual_weight 0, as in the reference)
-        (l_pix if l_g_percep is None else l_pix + l_g_percep).backward()
+        if self.net_d is not None:
+            self._critic_step()
+            k = self._step - self.net_g_pretrain_steps
+            if k % self.net_d_steps != 0 or k <= self.net_d_init_steps:
+                return
+        l_g_total = l_pix
+        l_g_percep = None
+        if self.cri_perceptual is not None:
+            l_g_percep, _ = self.cri_perceptual(self.output, self.gt)   # (None with perceptual_weight 0, as in the reference)
+        if l_g_percep is not None:
+            l_g_total = l_g_total + l_g_percep
+        l_g_gan = None
+        if self.net_d is not None:
+            # the critic is a fixed function in the generator's step: no gradient buffers for its parameters
+            params_d = list(self.net_d.parameters())
+            for p in params_d:
+                p.requires_grad = False
+            try:
+                l_g_gan = self.cri_gan(self.net_d(self.output), True, is_disc=False)
+                l_g_total = l_g_total + l_g_gan
+                l_g_total.backward()
+            finally:
+                for p in params_d:
+                    p.requires_grad = True
+        else:
+            l_g_total.backward()
         self.optimizer_g.step()
         self.log_dict['l_g_pix'] = l_pix.detach()
         if l_g_percep is not None:
             self.log_dict['l_g_percep'] = l_g_percep.detach()
+        if l_g_gan is not None:
+            self.log_dict['l_g_gan'] = l_g_gan.detach()
+
+    def _critic_step(self):
+        """One update of the critic on D(gt), D(output.detach()) and the gradient penalty (ref_restoration_model.py:209-232).
+        The penalty gets the detached output: the critic's backward must not free the generator's graph, which the generator's
+        step still needs, and no gradient reaches the generator through the penalty in the reference either."""
+        self.optimizer_d.zero_grad()
+        fake = self.output.detach()
+        real_d_pred = self.net_d(self.gt)
+        l_d_real = self.cri_gan(real_d_pred, True, is_disc=True)
+        fake_d_pred = self.net_d(fake)
+        l_d_fake = self.cri_gan(fake_d_pred, False, is_disc=True)
+        l_d_total = l_d_real + l_d_fake
+        l_grad_penalty = None
+        if self.cri_grad_penalty is not None:
+            l_grad_penalty = self.cri_grad_penalty(self.net_d, self.gt, fake)
+            l_d_total = l_d_total + l_grad_penalty
+        l_d_total.backward()
+        self.optimizer_d.step()
+        self.log_dict['l_d_real'] = l_d_real.detach()
+        self.log_dict['out_d_real'] = real_d_pred.detach().mean()
+        self.log_dict['l_d_fake'] = l_d_fake.detach()
+        self.log_dict['out_d_fake'] = fake_d_pred.detach().mean()
+        if l_grad_penalty is not None:
+            self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
 
     GRAPH_WARMUP_STEPS = 2
 
@@ -190,6 +289,13 @@ class RefRestorationModel(BaseModel):
         self._graph = graph
         self._graph_output = self.output       # the tensor every replay rewrites in place
         graph.replay()
+
+    def save(self, epoch, current_iter):
+        """net_g, net_d when there is one, and the training state (ref_restoration_model.py:289-293)."""
+        self.save_network(self.net_g, 'net_g', current_iter)
+        if getattr(self, 'net_d', None) is not None:
+            self.save_network(self.net_d, 'net_d', current_iter)
+        self.save_training_state(epoch, current_iter)
 
     # ---------------------------------------------------------------- validation
     def get_current_visuals(self):
